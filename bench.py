@@ -9,8 +9,13 @@ prompt (untimed), then untimed decode steps up to the timed window, W warmup tok
 among them, then K timed tokens.  The window is placed on the C2 trajectory so that its
 mean context is the trajectory's (383.5): the defaults (W=32, K=480) time positions
 160..639; a short window (e.g. the driver's K=20) is centred at position 374..393.
-Beside `value`, `c2_full` times the whole trajectory: all 512 decode tokens after a
-fresh 128-token prompt.
+
+A plain run (`--gpus 1 --steps K --warmup W`) does only what `value` needs: load, prefill,
+the untimed steps up to the window, the K timed steps, the result line.  `--dump-outputs
+DIR` also writes what the last timed step computed (dump_outputs).  Every other figure is
+a leg of `--full`: `c2_full` (the whole trajectory: all 512 decode tokens after a fresh
+128-token prompt), the per-class kernel times and the roofline they give, the warm
+prefill (TTFT), the other numerics mode, continuous batching and the CPU baseline.
 
 Multi-GPU (`torch.distributed.run --nproc-per-node N`): replicas only — each rank
 decodes its own stream (prompt seed 4+rank) with no data-path collective; rank 0's
@@ -50,6 +55,12 @@ def parse(argv=None):
     ap.add_argument("--preset", default="llama3-8b-q4km")
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--model-dir", default=os.environ.get("LLMI_BENCH_DIR", "/tmp/llmi_bench"))
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg reported beside `value`: per-class kernel times + roofline, c2_full, "
+                         "warm prefill (TTFT), the other numerics mode, continuous batching, the CPU baseline "
+                         "(each has its own switch below; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's outputs as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--profile-steps", type=int, default=20)
     ap.add_argument("--cpu-sample-tokens", type=int, default=20, help="timed CPU-baseline tokens (at the GPU window)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -67,7 +78,10 @@ def parse(argv=None):
                          "model of upstream's x86 AVX2 association (match with the reference's CPU image unpinned)")
     ap.add_argument("--no-other-numerics", action="store_true",
                     help="skip the leg that times the same window in the other numerics mode")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Dist:
@@ -226,11 +240,13 @@ class LlmiEngine:
         t = time.perf_counter()
         assert self.ctx.decode(self.prompt) == 0
         self.prefill_s = time.perf_counter() - t
-        # warm prefill (TTFT) of the same prompt: the KV cache is rebuilt identically
-        self.ctx.kv_clear()
-        t = time.perf_counter()
-        assert self.ctx.decode(self.prompt) == 0
-        self.prefill_warm_s = time.perf_counter() - t
+        self.prefill_warm_s = None
+        if args.full:
+            # warm prefill (TTFT) of the same prompt: the KV cache is rebuilt identically
+            self.ctx.kv_clear()
+            t = time.perf_counter()
+            assert self.ctx.decode(self.prompt) == 0
+            self.prefill_warm_s = time.perf_counter() - t
         self.next = self.ctx.greedy(-1)
         self.pos = len(self.prompt)
         self.generated: list[int] = []
@@ -243,6 +259,8 @@ class LlmiEngine:
         toks = self.ctx.generate_greedy(self.next, self.pos, n)
         self.generated += toks
         self.pos += n
+        self.last_in = toks[-2] if n > 1 else self.next  # the input token of the call's last step
+        self.last_toks = toks
         self.next = toks[-1]
         self.bytes, self.us = self.ctx.stats()
 
@@ -250,6 +268,35 @@ class LlmiEngine:
         import torch
 
         torch.cuda.synchronize()
+
+    def dump_outputs(self, out_dir: str) -> dict:
+        """--dump-outputs: what the timed call (generate_greedy over the K timed steps) handed
+        back and what its last step left on the device, for comparing two builds output
+        for output (same arguments -> same model file, prompt and window):
+          tokens.npy  float64 [K]       the K token ids the timed call returned
+          hidden.npy  float32 [n_embd]  the residual stream after the last layer of the last
+                                        timed step, read from the step's own buffer
+          logits.npy  float32 [n_vocab] the last timed step's logits.  generate_greedy keeps
+                                        them on the device and returns their argmax, so the
+                                        step is run once more through llama_decode (same
+                                        token, same position, the same step kernels; its KV
+                                        row is rewritten with the same values); the rerun
+                                        must reproduce hidden.npy bit for bit and the
+                                        returned token.
+        Call straight after the timed region, before any other leg touches the context."""
+        import numpy as np
+
+        os.makedirs(out_dir, exist_ok=True)
+        tokens = np.asarray(self.last_toks, dtype=np.float64)
+        hidden = self.ctx.tap(1, self.model.n_embd)
+        assert self.ctx.decode([self.last_in], pos=[self.pos - 1]) == 0
+        logits = self.ctx.logits(-1).astype(np.float32)
+        if not np.array_equal(self.ctx.tap(1, self.model.n_embd), hidden) or self.ctx.greedy(-1) != self.next:
+            raise RuntimeError("dump_outputs: the rerun of the last timed step differs from the timed one")
+        out = {"tokens": tokens, "hidden": hidden, "logits": logits}
+        for name, a in out.items():
+            np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        return {name: list(a.shape) for name, a in out.items()}
 
     def c2_full(self) -> dict:
         """The whole C2 trajectory: the 128-token prompt again (KV cache rebuilt), then all
@@ -517,15 +564,20 @@ def main(argv=None):
     # end-to-end roofline: algorithmic bytes of the timed tokens / time (this rank)
     e2e_gbps = eng.bytes / (eng.us * 1e-6) / 1e9 if eng.us > 0 else 0.0
     window = (eng.pos - args.steps, eng.pos)
-    prof = eng.profile(args.profile_steps) if args.profile_steps > 0 else {}
-    c2 = eng.c2_full() if not args.no_c2_full and args.prompt == C2_PROMPT else None
+    dumped = None
+    if args.dump_outputs and dist.rank == 0:
+        dumped = eng.dump_outputs(args.dump_outputs)
+        log(f"wrote {sorted(dumped)} to {args.dump_outputs}")
+    full = args.full
+    prof = eng.profile(args.profile_steps) if full and args.profile_steps > 0 else {}
+    c2 = eng.c2_full() if full and not args.no_c2_full and args.prompt == C2_PROMPT else None
     other = None
-    if not args.no_other_numerics:
+    if full and not args.no_other_numerics:
         try:
             other = eng.other_numerics(window)
         except Exception as e:  # reported beside the metric, never required
             log(f"other-numerics leg failed: {e}")
-    counts = [int(x) for x in args.batch_seqs.split(",") if x.strip()]
+    counts = [int(x) for x in args.batch_seqs.split(",") if x.strip()] if full else []
     batched = None
     if counts:
         try:
@@ -539,7 +591,7 @@ def main(argv=None):
         prof_c = committed_profile(args.profile_dir, args.preset)
         traffic = prof_c.get("hbm_bytes_per_launch")
         cpu = None
-        if n == 1 and not args.no_cpu_baseline:
+        if full and n == 1 and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(eng.path, eng.prompt, eng.generated, window,
                                    min(args.cpu_sample_tokens, window[1] - window[0]))
@@ -567,8 +619,11 @@ def main(argv=None):
                        "parallelism": f"replicas x{n} (RCCL weight fan-out)", "global_batch": n},
             "c2_full": c2,
             "numerics": args.numerics,
+            "full": full,
+            "outputs": dumped,
             "other_numerics": other,
-            "roofline": {"bound": "hbm", "kernel": f"k_matvec (ffn_gate+ffn_up {eng.gate_type} + SwiGLU)",
+            "roofline": None if not full else  # the per-class kernel times are a leg of --full
+                        {"bound": "hbm", "kernel": f"k_matvec (ffn_gate+ffn_up {eng.gate_type} + SwiGLU)",
                          "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
                          "traffic_source": (prof_c.get("source") if traffic else
@@ -586,7 +641,8 @@ def main(argv=None):
                              "per_step": v["launches_per_step"]} for k2, v in prof.items()},
             "load_s": round(eng.load_s, 2),
             "upload_s": round(eng.model.upload_s, 3),
-            "prefill": {"tokens": args.prompt, "path": "mfma" if eng.model.prefill_supported else "decode-steps",
+            "prefill": None if not full else  # the warm prefill is a leg of --full
+                       {"tokens": args.prompt, "path": "mfma" if eng.model.prefill_supported else "decode-steps",
                         "ttft_ms": round(eng.prefill_warm_s * 1e3, 2),
                         "tok_per_s": round(args.prompt / max(eng.prefill_warm_s, 1e-9), 1)},
             "fanout_s": round(eng.fanout_s, 3),

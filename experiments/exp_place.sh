@@ -5,7 +5,7 @@ set -u
 OUT=gpurun_out/place; mkdir -p $OUT
 run() {  # name preset env...
   local n=$1 p=$2; shift 2
-  env "$@" timeout -k 10 300 python -u bench.py --preset $p --no-cpu-baseline --batch-seqs= --no-other-numerics \
+  env "$@" timeout -k 10 300 python -u bench.py --full --preset $p --no-cpu-baseline --batch-seqs= --no-other-numerics \
     --steps 100 --warmup 16 --profile-steps 0 > $OUT/${p}_$n.json 2> $OUT/${p}_$n.err || exit 1
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], sys.argv[3], d['value'], d.get('c2_full',{}).get('tok_s'))" $OUT/${p}_$n.json $p $n
 }

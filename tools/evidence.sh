@@ -49,14 +49,14 @@ final)
   rc=$?
   tail -3 "$OUT/gpu_tests.txt"
   [ $rc -ne 0 ] && { grep -E "FAILED|ERROR" "$OUT/gpu_tests.txt" | head -20; exit 2; }
-  timeout -k 10 600 python -u bench.py > "$OUT/bench_default.log" 2>&1 || { tail -5 "$OUT/bench_default.log"; exit 3; }
+  timeout -k 10 600 python -u bench.py --full > "$OUT/bench_default.log" 2>&1 || { tail -5 "$OUT/bench_default.log"; exit 3; }
   tail -1 "$OUT/bench_default.log" > "$OUT/bench_default.json"
   python3 -c "import json; d=json.load(open('$OUT/bench_default.json')); print(d['value'], d['roofline']['frac'], (d.get('c2_full') or {}).get('tok_s'))"
   ;;
 config)
   P=${1:?preset}; shift
   mkdir -p "$OUT/prof_$P"
-  ARGS="--preset $P --no-cpu-baseline --batch-seqs= --no-other-numerics --steps 100 --warmup 16 --profile-steps 0"
+  ARGS="--full --preset $P --no-cpu-baseline --batch-seqs= --no-other-numerics --steps 100 --warmup 16 --profile-steps 0"
   ( cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/prof_$P/stats" -o run -- \
       python3 "$R/bench.py" $ARGS "$@" > "$R/$OUT/prof_$P/stats.json" 2> "$R/$OUT/prof_$P/stats.err" ) || { tail -5 "$OUT/prof_$P/stats.err"; exit 1; }
   # counters on eager launches (graph replays under --pmc crashed the profiler's host side)
@@ -64,7 +64,7 @@ config)
       python3 "$R/bench.py" $ARGS "$@" --eager --steps 20 > "$R/$OUT/prof_$P/pmc.json" 2> "$R/$OUT/prof_$P/pmc.err" ) || { tail -5 "$OUT/prof_$P/pmc.err"; exit 2; }
   python3 tools/make_traffic.py "$OUT/prof_$P" "$P" > /dev/null || exit 3
   trim "$OUT/prof_$P"
-  timeout -k 10 600 python -u bench.py --no-cpu-baseline --preset "$P" --profile-dir "$OUT/prof_$P" "$@" \
+  timeout -k 10 600 python -u bench.py --full --no-cpu-baseline --preset "$P" --profile-dir "$OUT/prof_$P" "$@" \
       > "$OUT/bench_$P.log" 2>&1 || { tail -5 "$OUT/bench_$P.log"; exit 4; }
   tail -1 "$OUT/bench_$P.log" > "$OUT/bench_$P.json"
   python3 -c "import json; d=json.load(open('$OUT/bench_$P.json')); r=d['roofline']; print('$P', d['value'], 'frac', r['frac'], 'rocprof_frac', r.get('rocprof_frac'), 'traffic', r.get('traffic'), 'c2', (d.get('c2_full') or {}).get('tok_s'))"
@@ -72,7 +72,7 @@ config)
 kernels)
   P=${1:-llama3-8b-q4km}
   mkdir -p "$OUT/kc_$P"
-  ARGS="--preset $P --no-cpu-baseline --batch-seqs= --no-other-numerics --no-c2-full --eager --steps 12 --warmup 4 --profile-steps 0"
+  ARGS="--full --preset $P --no-cpu-baseline --batch-seqs= --no-other-numerics --no-c2-full --eager --steps 12 --warmup 4 --profile-steps 0"
   i=0
   for set in "FETCH_SIZE" "$SQ1" "$SQ2"; do
     i=$((i+1))
@@ -130,12 +130,12 @@ prefill)
 batch)
   SEQS=${1:-8}
   ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/batch" -o run -- \
-      python3 "$R/bench.py" --no-cpu-baseline --preset llama3-8b-q4km --prompt 128 --steps 16 --warmup 4 --profile-steps 0 \
+      python3 "$R/bench.py" --full --no-cpu-baseline --preset llama3-8b-q4km --prompt 128 --steps 16 --warmup 4 --profile-steps 0 \
       --no-c2-full --no-other-numerics --batch-seqs "$SEQS" > "$R/$OUT/batch.log" 2>&1 ) || { tail -5 "$OUT/batch.log"; exit 1; }
   trim "$OUT/batch"
   stats_top "$OUT/batch" 16 | tee "$OUT/batch_stats.txt"
   ( cd /tmp && timeout -s KILL 300 rocprofv3 --pmc $SQ1 --kernel-trace --output-format csv -d "$R/$OUT/batch_sq" -o run -- \
-      python3 "$R/bench.py" --no-cpu-baseline --preset llama3-8b-q4km --prompt 128 --steps 8 --warmup 2 --profile-steps 0 \
+      python3 "$R/bench.py" --full --no-cpu-baseline --preset llama3-8b-q4km --prompt 128 --steps 8 --warmup 2 --profile-steps 0 \
       --no-c2-full --no-other-numerics --eager --batch-seqs "$SEQS" --batch-steps 8 > "$R/$OUT/batch_sq.log" 2>&1 ) || { tail -5 "$OUT/batch_sq.log"; exit 2; }
   python3 tools/sq_summary.py "$OUT/batch_sq" k_bm > "$OUT/batch_sq_bmm.json"  # k_bmd / k_bmd2 (default) and k_bmm
   trim "$OUT/batch_sq"
@@ -145,7 +145,7 @@ envab)
   i=0
   for cfg in "$@"; do
     i=$((i+1)); envs=(); [ "$cfg" != "-" ] && envs=($cfg)
-    timeout -k 10 300 env "${envs[@]}" python bench.py --no-cpu-baseline --no-other-numerics ${BENCH_ARGS:-} > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"
+    timeout -k 10 300 env "${envs[@]}" python bench.py --full --no-cpu-baseline --no-other-numerics ${BENCH_ARGS:-} > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"
     rc=$?; echo "[$i] $cfg rc=$rc"; [ $rc -ne 0 ] && { tail -5 "$OUT/bench_$i.err"; exit $rc; }
     python3 - "$OUT/bench_$i.json" <<'PY'
 import json, sys
