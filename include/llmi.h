@@ -62,8 +62,10 @@ struct llama_model_params {
 /* OR-ed into either: decode attention in ggml's CPU flash-attention numerics (online
  * softmax, f16 V accumulation, glibc expf; what a llama-server without --flash-attn runs
  * when -fa auto resolves to on), oracle flag OR_X86_FA.  Such a model runs prompts as
- * decode steps (batched steps advance its sequences together, the flash attention of
- * every slot in one launch); up to 8192 positions. */
+ * decode steps unless LLMI_FA_PREFILL=1 is in the environment (opt-in, off by default,
+ * read on every call: the batched prefill with k_pf_attn_fa, the same bits);
+ * batched steps advance its sequences together, the flash attention of every slot in
+ * one launch; up to 8192 positions. */
 #define LLMI_NUMERICS_FA 2
 
 /* upstream llama_context_params (subset) */
@@ -228,7 +230,8 @@ int32_t llmi_profile_kernels(struct llama_context* ctx, llama_token first, int32
  *                     xspin_limit 0: every such wait gives up at once; fault-path test)
  *   "numerics"        this thread's numerics for the kernel-level entry points below
  *                     (llmi_repack's byte order, llmi_matvec, llmi_quantize_act,
- *                     llmi_attention, llmi_pf_attention): LLMI_NUMERICS_* */
+ *                     llmi_attention, llmi_pf_attention, llmi_pf_attention_fa):
+ *                     LLMI_NUMERICS_* */
 int32_t llmi_test_option(const char* name, int32_t value);
 /* Algorithmic bytes of one decode step at KV length n_kv (weights + one embedding row
  * + norms + KV read/write), the numerator of achieved GB/s. */
@@ -236,9 +239,13 @@ double llmi_bytes_per_token(const struct llama_model* model, int32_t n_kv);
 /* 1 when llama_decode runs a prompt (a leading run of >= 2 tokens at consecutive
  * positions that need no logits) through the batched MFMA prefill path (one launch per
  * op over all its tokens; bit-identical to decode steps), 0 when every token of such a
- * batch is a decode step (shapes the prefill kernels do not take).  LLMI_NO_PREFILL=1
- * in the environment forces decode steps. */
+ * batch is a decode step (shapes the prefill kernels do not take; a LLMI_NUMERICS_FA
+ * model unless LLMI_FA_PREFILL=1 is in the environment, read on every call).
+ * LLMI_NO_PREFILL=1 in the environment forces decode steps, whatever this returns. */
 int32_t llmi_prefill_supported(const struct llama_model* model);
+/* Tokens this context has sent through the batched prefill path since it was created
+ * (the results are bit-identical either way; this tells which path ran). */
+int64_t llmi_prefill_token_count(const struct llama_context* ctx);
 /* Device weight arena (for RCCL broadcast by a caller that owns the communicator). */
 int32_t llmi_model_arena(const struct llama_model* model, void** dev_ptr, uint64_t* bytes);
 /* Replica check: an order-independent 64-bit hash of the model's device arena (sum over
@@ -351,6 +358,15 @@ int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
 double llmi_pf_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
                          const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode,
                          int64_t scratch_bytes);
+/* One batched-prefill attention in the flash-attention numerics (k_pf_attn_fa, what
+ * prefill_enqueue launches for a LLMI_NUMERICS_FA model under LLMI_FA_PREFILL=1):
+ * arguments and layouts as llmi_pf_attention, the dot association from this thread's
+ * "numerics" test option (bit LLMI_NUMERICS_X86), pos0 + T <= 8192.  Row t equals
+ * llmi_attention over n_kv = pos0 + t + 1 positions in the same association |
+ * LLMI_NUMERICS_FA bit for bit.  Bad arguments are rejected before any device call.
+ * Returns elapsed device microseconds (>= 0) or < 0 on error. */
+double llmi_pf_attention_fa(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
+                            const float* q, const uint16_t* kc, const uint16_t* vc, float* out);
 /* Attention microbenchmark: n_kv positions, one launch per layer over >= 512 MB of
  * distinct KV caches, graph-replayed `reps` times; microseconds per launch (< 0 error).
  * mode: 0 auto, 1 fused, 2 split, 3 two-kernel.  trace_dev != NULL (LLMI_EXP_TRACE

@@ -143,7 +143,9 @@ LLMI_HD uint64_t llmi_exp2f_tab(uint32_t i) {  /* asuint64(2^(i/32)) - (i << 47)
     }
 }
 LLMI_HD double llmi_fma_d(double a, double b, double c, int fma) { return fma ? __builtin_fma(a, b, c) : a * b + c; }
-LLMI_HD float llmi_expf_glibc(float x, int fma) {
+/* tab: NULL, or the caller's copy of the 32 llmi_exp2f_tab words (a GPU kernel keeps it
+ * in LDS: the switch above is a 32-way divergent branch tree when the index varies by lane) */
+LLMI_HD float llmi_expf_glibc_tab(float x, int fma, const uint64_t* tab) {
     const uint32_t abstop = (llmi_f2u(x) >> 20) & 0x7ffu;
     if (abstop >= 0x42bu) {                 /* |x| >= 88 or nan (top12(88.0f) = 0x42b) */
         if (llmi_f2u(x) == 0xff800000u) return 0.0f;
@@ -162,7 +164,7 @@ LLMI_HD float llmi_expf_glibc(float x, int fma) {
     kd -= SHIFT;
     const double r = fma ? __builtin_fma(InvLn2N, xd, -kd) : InvLn2N * xd - kd;
     double z;
-    const uint64_t t = llmi_exp2f_tab((uint32_t)ki) + (ki << 47);
+    const uint64_t t = (tab ? tab[(uint32_t)ki & 31u] : llmi_exp2f_tab((uint32_t)ki)) + (ki << 47);
     const double s = llmi_u2d(t);
     z = llmi_fma_d(C0, r, C1, fma);
     const double r2 = r * r;
@@ -171,6 +173,7 @@ LLMI_HD float llmi_expf_glibc(float x, int fma) {
     y = y * s;
     return (float)y;
 }
+LLMI_HD float llmi_expf_glibc(float x, int fma) { return llmi_expf_glibc_tab(x, fma, 0); }
 
 /* ggml SiLU: x / (1 + exp(-x)) with the shared exp. */
 LLMI_HD float llmi_silu(float x) { return x / (1.0f + llmi_expf(-x)); }

@@ -225,7 +225,8 @@ static void copy_out(llama_context* ctx, int r, const float* logits_dev, const S
 // One sequence's tokens (batch indices idx, positions pos) through the single-sequence
 // path: the batched prefill of the leading run of consecutive, logit-less tokens (leaving
 // at least the last token to a decode step), then decode steps.
-// LLMI_NO_PREFILL=1 runs every token as a decode step.
+// LLMI_NO_PREFILL=1 runs every token as a decode step (and so does a flash-attention
+// numerics model without LLMI_FA_PREFILL=1: prefill_supported).
 static bool run_seq(llama_context* ctx, const llama_batch& batch, int seq, const std::vector<int>& idx,
                     const std::vector<int>& pos, const std::vector<int>& rows, double& bytes, std::string& err) {
     Context& c = ctx->c;
@@ -247,6 +248,7 @@ static bool run_seq(llama_context* ctx, const llama_batch& batch, int seq, const
         std::vector<int32_t> toks((size_t)run);
         for (int i = 0; i < run; ++i) toks[(size_t)i] = batch.token[idx[(size_t)i]];
         if (!prefill_enqueue(c, toks.data(), run, p0, err)) return false;
+        c.pf_tokens += run;
         for (int i = 0; i < run; ++i) bytes += bytes_per_token(*c.m, p0 + i + 1);
         i0 = run;
     }
@@ -737,6 +739,8 @@ double llmi_model_upload_s(const struct llama_model* model) { return model ? mod
 int32_t llmi_prefill_supported(const struct llama_model* model) {
     return model && prefill_supported(model->m) ? 1 : 0;
 }
+
+int64_t llmi_prefill_token_count(const struct llama_context* ctx) { return ctx ? ctx->c.pf_tokens : 0; }
 
 double llmi_bytes_per_token(const struct llama_model* model, int32_t n_kv) {
     return model ? bytes_per_token(model->m, n_kv) : 0.0;
@@ -1611,6 +1615,37 @@ double llmi_pf_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, in
     (void)hipEventDestroy(e1);
     (void)hipFree(wsc);
     if (e != hipSuccess) { set_err(std::string("llmi_pf_attention: ") + hip_err(e)); return -3; }
+    return (double)ms * 1e3;
+    API_CATCH(-5)
+}
+
+double llmi_pf_attention_fa(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
+                            const float* q, const uint16_t* kc, const uint16_t* vc, float* out) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || n_head / n_head_kv > 32 ||
+        (head_dim != 64 && head_dim != 128) || T <= 0 || pos0 < 0 || n_ctx % 256 || pos0 + T > n_ctx ||
+        pos0 + T > kFaMaxKV || !q || !kc || !vc || !out) {
+        set_err("llmi_pf_attention_fa: bad arguments");
+        return -1;
+    }
+    API_TRY
+    PfAttn at;
+    at.q = q; at.out = out; at.ldq = n_head * head_dim; at.kc = kc; at.vc = vc;
+    at.n_ctx = n_ctx; at.pos0 = pos0; at.gqa = n_head / n_head_kv; at.max_kv = pos0 + T;
+    at.scale = 1.0f / sqrtf((float)head_dim);
+    at.num = t_hook_numerics & NUMERICS_X86;
+    at.fa = 1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, nullptr);
+    hipError_t e = launch_pf_attn(at, n_head, head_dim, T, nullptr);
+    (void)hipEventRecord(e1, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    float ms = 0.f;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (e != hipSuccess) { set_err(std::string("llmi_pf_attention_fa: ") + hip_err(e)); return -3; }
     return (double)ms * 1e3;
     API_CATCH(-5)
 }

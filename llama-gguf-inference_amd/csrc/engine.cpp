@@ -968,7 +968,13 @@ bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& er
 // ---------------------------------------------------------------------------------
 bool prefill_supported(const Model& m) {
     const HParams& hp = m.hp;
-    if (m.fa) return false;  // flash-attention numerics: prompts as decode steps (attnfa.hip is decode-only)
+    // flash-attention numerics: prompts as decode steps unless LLMI_FA_PREFILL=1 (read on
+    // every call) opts in to k_pf_attn_fa (pfattnfa.hip, <= 32 heads per KV head)
+    if (m.fa) {
+        const char* e = getenv("LLMI_FA_PREFILL");
+        if (!e || atoi(e) == 0) return false;
+        if (hp.n_head_kv <= 0 || hp.n_head % hp.n_head_kv || hp.n_head / hp.n_head_kv > 32) return false;
+    }
     if (hp.head_dim != 128 && hp.head_dim != 64) return false;
     if (hp.n_rot % 2 || hp.n_rot > hp.head_dim) return false;
     for (const Layer& L : m.layers) {
@@ -1019,6 +1025,7 @@ static bool prefill_alloc(Context& c, std::string& err) {
 int prefill_max_kv(Context& c) {
     const HParams& hp = c.m->hp;
     const int lim = pf_max_kv();
+    if (c.m->fa) return std::min(c.n_ctx, kFaMaxKV);  // k_pf_attn_fa streams the keys: no score space
     if (c.m->numerics == NUMERICS_X86)  // k_pf_a86 keeps the G heads' scores in LDS
         return std::min(lim, pf_attn_x86_max_kv(hp.n_head, hp.n_head_kv, hp.head_dim));
     // the whole context only where the tiled kernel can run: its score scratch must exist
@@ -1090,6 +1097,7 @@ bool prefill_enqueue(Context& c, const int32_t* tokens, int n, int pos0, std::st
             at.scale = 1.0f / sqrtf((float)D);
             at.wsc = c.pf_wsc; at.wsc_bytes = c.pf_wsc_bytes;
             at.num = x86;
+            at.fa = m.fa;
             PFC(launch_pf_attn(at, hp.n_head, D, T, c.stream));
             // attn_output + residual
             PFC(launch_pf_quant(c.pf_att, nq, nullptr, 0.f, nq, act_kind(L.wo.type), T, c.pf_aq, c.pf_abs, c.pf_ad, c.pf_abf, c.stream, x86));

@@ -140,6 +140,7 @@ struct Context {
     void* pf_abf = nullptr;        // K-quants: bsum pairs as k_pf_gemm's sumi MFMA fragments
     float* pf_wsc = nullptr;       // k_pf_fa score scratch (pf_fa_scratch_bytes; null: LDS attention kernels)
     size_t pf_wsc_bytes = 0;
+    int64_t pf_tokens = 0;         // tokens sent through prefill_enqueue since creation (llmi_prefill_token_count)
     ~Context();
 };
 
@@ -174,7 +175,8 @@ bool step_enqueue(Context& c, int kv_bound, std::string& err);
 // run one step via the cached graph of its KV bucket (or eagerly)
 bool step_run(Context& c, int pos, std::string& err);
 double bytes_per_token(const Model& m, int n_kv);
-// batched prefill: can the model's layers run through the MFMA prefill path?
+// batched prefill: can the model's layers run through the MFMA prefill path?  (flash-
+// attention numerics: only with LLMI_FA_PREFILL=1, read on every call)
 bool prefill_supported(const Model& m);
 bool bstep_supported(const Model& m);  // batched steps in this model's numerics (engine.cpp)
 // positions the batched prefill's attention reaches: the context when the tiled kernel

@@ -217,6 +217,7 @@ struct PfAttn {
     float* wsc = nullptr;      // k_pf_fa score scratch (pf_fa_scratch_bytes), null: LDS kernels only
     size_t wsc_bytes = 0;
     int num = 0;               // numerics (MVArgs::num): 1 = k_pf_a86 (attn86.hip)
+    int fa = 0;                // flash-attention numerics: k_pf_attn_fa (pfattnfa.hip), num its association
 };
 // score scratch k_pf_fa wants for ubatches of T tokens over n_ctx positions (0: the
 // head shape has no tiled kernel); launches are chunked to fit a smaller scratch
@@ -280,6 +281,9 @@ hipError_t launch_attention_x86(const AttnArgs& a, int n_head, int n_head_kv, in
                                 int mode = 0);
 hipError_t launch_pf_attn_x86(const PfAttn& a, int n_head, int n_head_kv, int head_dim, int T, hipStream_t s);
 int pf_attn_x86_max_kv(int n_head, int n_head_kv, int head_dim);
+// flash-attention numerics prefill attention (pfattnfa.hip): T rows at pos0.., the bits of
+// T launch_attention_fa steps; pos0 + T <= kFaMaxKV, gqa <= 32 (hipErrorNotSupported)
+hipError_t launch_pf_attn_fa(const PfAttn& a, int n_head, int head_dim, int T, hipStream_t s);
 // writes the prologue's quantized activation in ggml block form (test hook)
 hipError_t launch_quant_dump(const MVArgs& a, int act, void* out, hipStream_t stream);
 hipError_t launch_stream_read(const void* p, size_t bytes, unsigned* out, int blocks, hipStream_t stream);

@@ -1269,6 +1269,7 @@ static hipError_t pf_attn_g_launch(const PfAttn& a, int n_head, int T, hipStream
 
 hipError_t launch_pf_attn(const PfAttn& a, int n_head, int head_dim, int T, hipStream_t s, int path) {
     if (head_dim != 128 && head_dim != 64) return hipErrorInvalidValue;
+    if (a.fa) return launch_pf_attn_fa(a, n_head, head_dim, T, s);
     if (a.num) return launch_pf_attn_x86(a, n_head, n_head / a.gqa, head_dim, T, s);
     if (path < 0) path = g_pf_attn_simple ? 2 : g_pf_attn_fa ? -1 : 1;
     if (path == 0) return pf_fa_dispatch(a, n_head, head_dim, T, s);

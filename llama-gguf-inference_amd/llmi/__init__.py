@@ -254,7 +254,8 @@ class Model:
 
     @property
     def prefill_supported(self) -> bool:
-        """Whether llama_decode prefills prompts with the batched MFMA path."""
+        """Whether llama_decode prefills prompts with the batched MFMA path (a flash-attention
+        numerics model: only while LLMI_FA_PREFILL=1 is in the environment)."""
         return bool(lib().llmi_prefill_supported(self._h))
 
     def arena(self) -> tuple[int, int]:
@@ -338,6 +339,11 @@ class Context:
         rc = int(lib().llama_decode(self._h, b))
         del keep
         return rc
+
+    @property
+    def prefill_tokens(self) -> int:
+        """Tokens this context has sent through the batched prefill path (llmi_prefill_token_count)."""
+        return int(lib().llmi_prefill_token_count(self._h))
 
     def eval(self, tokens: Sequence[int], n_past: int) -> int:
         n = len(tokens)

@@ -108,6 +108,7 @@ SIGNATURES = {
     "llmi_profile_kernels": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                          C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "llmi_prefill_supported": (C.c_int32, [_P]),
+    "llmi_prefill_token_count": (C.c_int64, [_P]),
     "llmi_debug_tap": (C.c_int32, [_P, C.c_int32, _P]),
     "llmi_pf_gemm": (C.c_int32, [C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_int32, _P,
                                  C.POINTER(C.c_double)]),
@@ -117,6 +118,8 @@ SIGNATURES = {
     "llmi_attention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32]),
     "llmi_pf_attention": (C.c_double, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                        _P, C.c_int32, C.c_int64]),
+    "llmi_pf_attention_fa": (C.c_double, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                          _P]),
     "llmi_replicate": (C.c_int32, [_P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
     "llmi_rccl_unique_id": (C.c_int32, [C.c_char_p, C.c_int32]),
     "llmi_model_fanout": (C.c_int32, [_P, C.c_char_p, C.c_int32, C.c_int32]),
