@@ -126,6 +126,7 @@ float* llama_get_logits(struct llama_context* ctx);
 float* llama_get_logits_ith(struct llama_context* ctx, int32_t i);
 
 /* ---------- model / context introspection ---------- */
+/* owned by the model: valid on any thread until llama_model_free */
 const struct llama_vocab* llama_model_get_vocab(const struct llama_model* model);
 int32_t llama_vocab_n_tokens(const struct llama_vocab* vocab);
 llama_token llama_vocab_bos(const struct llama_vocab* vocab);

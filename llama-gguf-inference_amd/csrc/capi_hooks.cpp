@@ -1,0 +1,652 @@
+// capi_hooks.cpp — the test, profiling and microbenchmark hooks of include/llmi.h: whole
+// steps under a profiler or tracer, the test options and taps, and the kernel-level
+// entry points that launch one kernel without a model.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/llmi.h"
+#include "capi_internal.h"
+
+using namespace llmi;
+
+extern "C" {
+
+int32_t llmi_profile_kernels(struct llama_context* ctx, llama_token first, int32_t pos0, int32_t n_steps, double* us,
+                             double* bytes, int32_t* launches) {
+    API_TRY
+    if (!ctx || n_steps <= 0 || !us || !bytes || !launches) { set_err("llmi_profile_kernels: bad arguments"); return -1; }
+    Context& c = ctx->c;
+    if (first < 0 || first >= c.m->hp.n_vocab || pos0 < 0 || pos0 >= c.n_ctx) {
+        set_err("llmi_profile_kernels: token/position out of range");
+        return -1;
+    }
+    (void)hipSetDevice(c.m->device);
+    // In situ: n_steps whole decode steps at position pos0 (the decode graph's exact
+    // kernels, grids and arguments, in their order), launched one by one with EVERY
+    // kernel armed with an event pair that the runtime records when it starts and ends
+    // (hipExtLaunchKernelGGL): each kernel's execution time in its real place in the
+    // step (caches as its predecessor leaves them), without launch gaps.  One warm step
+    // first.  No tokens are consumed: the state is reset to (first, pos0) afterwards.
+    const int kv_bound = std::min(c.n_ctx, (pos0 / 256 + 1) * 256);
+    std::string err;
+    int rc = 0;
+    {
+        Prof warm;
+        if (launch_state_set(c.st, first, pos0, c.stream) != hipSuccess) { set_err("state set failed"); return -3; }
+        c.prof = &warm;
+        bool ok = step_enqueue(c, kv_bound, err);
+        Prof pk;
+        pk.timed = true;
+        for (int r = 0; ok && r < n_steps; ++r) {
+            if (launch_state_set(c.st, first, pos0, c.stream) != hipSuccess) { ok = false; break; }
+            c.prof = &pk;
+            ok = step_enqueue(c, kv_bound, err);
+        }
+        c.prof = nullptr;
+        if (!ok || hipStreamSynchronize(c.stream) != hipSuccess) {
+            set_err("llmi_profile_kernels: " + (err.empty() ? std::string("launch failed") : err));
+            rc = -4;
+        }
+        for (int k = 0; rc == 0 && k < K_NCLASS; ++k) {
+            int used = 0;
+            const double t = pk.elapsed_us(k, &used);
+            const int n = std::max(1, pk.launches[k]);
+            us[k] = used ? t / (double)used : 0.0;
+            bytes[k] = (pk.bytes[k] + pk.per_kv[k] * (double)(pos0 + 1)) / n;
+            launches[k] = pk.launches[k] / n_steps;
+        }
+    }
+    if (launch_state_set(c.st, first, pos0, c.stream) != hipSuccess || hipStreamSynchronize(c.stream) != hipSuccess) {
+        if (rc == 0) { set_err("llmi_profile_kernels: state reset failed"); rc = -4; }
+    }
+    c.n_past = pos0;
+    return rc;
+    API_CATCH(-5)
+}
+
+
+int32_t llmi_engine_trace(struct llama_context* ctx, llama_token first, int32_t pos0, int32_t layer, uint64_t* out,
+                          int64_t n_out) {
+    API_TRY
+    if (!ctx || !out) { set_err("llmi_engine_trace: bad arguments"); return -1; }
+    Context& c = ctx->c;
+    if (first < 0 || first >= c.m->hp.n_vocab || pos0 < 0 || pos0 >= c.n_ctx || layer < 0 || layer >= c.m->hp.n_layer) {
+        set_err("llmi_engine_trace: token/position/layer out of range");
+        return -1;
+    }
+    (void)hipSetDevice(c.m->device);
+    int cus = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.m->device);
+    const size_t n = (size_t)cus * 16 * 32;
+    if ((size_t)n_out < n) { set_err("llmi_engine_trace: out holds fewer than CUs x 512 stamps"); return -1; }
+    // one eager warm step, then one traced step at (first, pos0); the state is reset after
+    const int kv_bound = std::min(c.n_ctx, (pos0 / 256 + 1) * 256);
+    std::string err;
+    int rc = 0;
+    if (!c.le_trace && hipMalloc(&c.le_trace, n * 8) != hipSuccess) { set_err("llmi_engine_trace: hipMalloc"); return -3; }
+    (void)hipMemsetAsync(c.le_trace, 0, n * 8, c.stream);
+    bool ok = launch_state_set(c.st, first, pos0, c.stream) == hipSuccess && step_enqueue(c, kv_bound, err);
+    c.le_trace_layer = layer;
+    ok = ok && launch_state_set(c.st, first, pos0, c.stream) == hipSuccess && step_enqueue(c, kv_bound, err);
+    c.le_trace_layer = -1;
+    if (!ok || hipMemcpyAsync(out, c.le_trace, n * 8, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+        hipStreamSynchronize(c.stream) != hipSuccess) {
+        set_err("llmi_engine_trace: " + (err.empty() ? std::string("launch failed") : err));
+        rc = -4;
+    }
+    if (launch_state_set(c.st, first, pos0, c.stream) != hipSuccess || hipStreamSynchronize(c.stream) != hipSuccess)
+        if (rc == 0) { set_err("llmi_engine_trace: state reset failed"); rc = -4; }
+    c.n_past = pos0;
+    return rc == 0 ? cus : rc;
+    API_CATCH(-5)
+}
+
+double llmi_le_stream_bench(const void* src, int64_t bytes, int32_t mode, int32_t iters, int32_t nt) {
+    return le_stream_bench(src, (size_t)bytes, mode, iters, nt);
+}
+
+// numerics of this thread's kernel-level entry points (llmi_test_option "numerics")
+static thread_local int t_hook_numerics = 0;
+
+int32_t llmi_test_option(const char* name, int32_t value) {
+    if (!name) return -1;
+    int* opt = nullptr;
+    if (!strcmp(name, "numerics")) {
+        const int old = t_hook_numerics;
+        if (value >= 0 && value <= (NUMERICS_X86 | NUMERICS_FA)) t_hook_numerics = value;
+        else if (value >= 0) { set_err("llmi_test_option: numerics must be 0..3"); return -1; }
+        return old;
+    }
+    if (!strcmp(name, "pf_attn_simple")) opt = &g_pf_attn_simple;
+    else if (!strcmp(name, "pf_fa_noalloc")) opt = &g_pf_fa_noalloc;
+    else if (!strcmp(name, "pf_attn_fa")) opt = &g_pf_attn_fa;
+    else if (!strcmp(name, "pf_gemm_ng")) opt = &g_pf_gemm_ng;
+    else if (!strcmp(name, "pf_qkv_merge")) opt = &g_pf_qkv_merge;
+    else if (!strcmp(name, "pf_xcd_map")) opt = &g_pf_xcd_map;
+    else if (!strcmp(name, "pf_quant_bpc")) opt = &g_pf_quant_bpc;
+    else if (!strcmp(name, "pf_quant_split_below")) opt = &g_pf_quant_split_below;
+    else if (!strcmp(name, "pf_fa_cfg")) opt = &g_pf_fa_cfg;
+    else if (!strcmp(name, "pf_max_kv")) opt = &g_pf_max_kv;
+    else if (!strcmp(name, "xspin_limit")) opt = &g_xspin_limit;
+    else if (!strcmp(name, "xtag_skew")) opt = &g_xtag_skew;
+    else if (!strcmp(name, "engine")) opt = &g_le_on;      // layer engine on/off (contexts made after)
+    else if (!strcmp(name, "le_spin")) opt = &g_le_spin;   // layer engine's bounded-wait polls
+    if (!opt) { set_err("llmi_test_option: unknown option"); return -1; }
+    const int old = *opt;
+    if (value >= 0) *opt = value;
+    return old;
+}
+
+int32_t llmi_debug_tap(struct llama_context* ctx, int32_t which, float* out) {
+    if (!ctx || !out) { set_err("llmi_debug_tap: bad arguments"); return -1; }
+    Context& c = ctx->c;
+    const HParams& hp = c.m->hp;
+    (void)hipSetDevice(c.m->device);
+    if (which == 7 || which == 8) {  // last layer's K ([HK][n_ctx][D]) or V ([HK][D][n_ctx]) cache, raw f16
+        const size_t kvl = (size_t)hp.n_head_kv * c.n_ctx * hp.head_dim;
+        const uint16_t* base = (which == 7 ? c.kc : c.vc) + (size_t)(hp.n_layer - 1) * kvl;
+        hipError_t e = hipMemcpyAsync(out, base, kvl * 2, hipMemcpyDeviceToHost, c.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+        if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
+        return 0;
+    }
+    if (which >= 11 && which <= 15) {  // batched-step buffers, kMaxBatch rows each
+        const float* b = which == 11 ? c.bx : which == 12 ? c.bq : which == 13 ? c.batt : which == 14 ? c.bh : c.blogits;
+        const size_t per = which == 11 ? hp.n_embd : which == 14 ? hp.n_ff : which == 15 ? hp.n_vocab
+                                                                                     : (size_t)hp.n_head * hp.head_dim;
+        if (!b) { set_err("llmi_debug_tap: no batched step ran"); return -1; }
+        hipError_t e = hipMemcpy(out, b, per * kMaxBatch * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
+        return 0;
+    }
+    if (which == 0) {  // the last step's embedding row (get_rows), recomputed by k_embed's dequant
+        float* tmp = nullptr;
+        if (hipMalloc(&tmp, (size_t)hp.n_embd * 4) != hipSuccess) { set_err("out of device memory"); return -2; }
+        EmbArgs ea;
+        ea.w = seg_of(*c.m, c.m->tok_embd, 0);
+        ea.cols = hp.n_embd;
+        ea.vocab = hp.n_vocab;
+        hipError_t e = launch_embed_row(ea, c.st, tmp, c.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, (size_t)hp.n_embd * 4, hipMemcpyDeviceToHost, c.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+        (void)hipFree(tmp);
+        if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
+        return 0;
+    }
+    const float* src = which == 1 ? c.x : which == 2 ? c.q : which == 3 ? c.att : which == 4 ? c.h : nullptr;
+    const size_t n = which == 1 ? hp.n_embd : which == 4 ? hp.n_ff : (size_t)hp.n_head * hp.head_dim;
+    if (!src) { set_err("llmi_debug_tap: unknown tap"); return -1; }
+    (void)hipSetDevice(c.m->device);
+    hipError_t e = hipMemcpyAsync(out, src, n * 4, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
+    return 0;
+}
+
+// ---------------- kernel-level entry points (tests / microbenchmarks) ----------------
+static Seg seg_at(int32_t type, const void* w, int64_t rows, int64_t cols) {
+    DevMat dm;
+    dm.type = type;
+    dm.rows = rows;
+    dm.cols = cols;
+    plan_planes(dm, 0);
+    Seg s;
+    s.a = (const uint8_t*)w + dm.off_a;
+    s.h = (const uint8_t*)w + dm.off_h;
+    s.s = (const uint8_t*)w + dm.off_s;
+    s.d = (const uint8_t*)w + dm.off_d;
+    s.type = type;
+    s.rows = (int)rows;
+    s.row0 = 0;
+    s.rgs = dm.rgs;
+    s.x86 = (t_hook_numerics & NUMERICS_X86) != 0;
+    return s;
+}
+
+int64_t llmi_device_layout_bytes(int32_t type, int64_t rows, int64_t cols) {
+    if (!type_supported(type) || cols % block_elems(type)) return -1;
+    DevMat dm;
+    dm.type = type; dm.rows = rows; dm.cols = cols;
+    return (int64_t)plan_planes(dm, 0);
+}
+
+int32_t llmi_repack(int32_t type, const void* raw, void* w, int64_t rows, int64_t cols) {
+    if (!type_supported(type) || cols % block_elems(type)) { set_err("bad type/shape"); return -1; }
+    DevMat dm;
+    dm.type = type; dm.rows = rows; dm.cols = cols;
+    plan_planes(dm, 0);
+    hipError_t e;
+    if (needs_repack(type)) {
+        e = launch_repack(type, raw, (uint8_t*)w + dm.off_a, (uint8_t*)w + dm.off_h, (uint8_t*)w + dm.off_s,
+                          (uint8_t*)w + dm.off_d, rows * (cols / block_elems(type)), cols, dm.rgs,
+                          (t_hook_numerics & NUMERICS_X86) != 0, nullptr);
+    } else {
+        e = hipMemcpy(w, raw, dm.bytes, hipMemcpyDeviceToDevice);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
+    return 0;
+}
+
+int32_t llmi_matvec(int32_t type, const void* w, int64_t rows, int64_t cols, const float* x, const float* nw, float eps,
+                    float* y, int32_t mode) {
+    if (!(type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0) || cols % 256 || rows <= 0) {
+        set_err("llmi_matvec: unsupported type/shape");
+        return -1;
+    }
+    MVArgs a;
+    a.seg[0] = seg_at(type, w, rows, cols);
+    a.nseg = 1;
+    a.cols = (int)cols;
+    a.npairs = (int)((rows + 1) / 2);
+    a.x = x; a.nw = nw; a.eps = eps; a.y = y;
+    a.num = t_hook_numerics & NUMERICS_X86;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    hipDeviceProp_t prop;
+    (void)hipGetDeviceProperties(&prop, dev);
+    hipError_t e = launch_matvec(a, mode == 1 ? EPI_ADD : EPI_STORE, std::max(64, prop.multiProcessorCount * wg_per_cu()), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
+    return 0;
+}
+
+int32_t llmi_pf_gemm(int32_t type, const void* w, int64_t rows, int64_t cols, const float* x, const float* nw, float eps,
+                     int32_t n_tok, float* y, double* usec) {
+    if (!pf_gemm_ok(type, (int)rows, (int)cols) || n_tok <= 0) { set_err("llmi_pf_gemm: unsupported type/shape"); return -1; }
+    const int x86 = (t_hook_numerics & NUMERICS_X86) != 0;
+    const int tpad = (n_tok + 63) / 64 * 64;
+    void* aq = nullptr;
+    int16_t* abs = nullptr;
+    float* ad = nullptr;
+    void* abf = nullptr;
+    hipError_t e = hipMalloc(&aq, (size_t)tpad * cols * 2);
+    if (e == hipSuccess) e = hipMalloc(&abf, (size_t)tpad * (cols / 256) * 64);
+    if (e == hipSuccess) e = hipMemset(abf, 0, (size_t)tpad * (cols / 256) * 64);
+    if (e == hipSuccess) e = hipMalloc(&abs, (size_t)tpad * (cols / 16) * 2);
+    if (e == hipSuccess) e = hipMalloc(&ad, (size_t)tpad * (cols / 32) * 4);
+    if (e == hipSuccess) e = hipMemset(aq, 0, (size_t)tpad * cols * 2);
+    if (e == hipSuccess) e = hipMemset(abs, 0, (size_t)tpad * (cols / 16) * 2);
+    if (e == hipSuccess) e = hipMemset(ad, 0, (size_t)tpad * (cols / 32) * 4);
+    if (e == hipSuccess) e = launch_pf_quant(x, (int)cols, nw, eps, (int)cols, act_kind(type), n_tok, aq, abs, ad, abf, nullptr, x86);
+    PfGemm g;
+    g.w = seg_at(type, w, rows, cols); g.rows = (int)rows; g.cols = (int)cols; g.T = n_tok;
+    g.aq = aq; g.abs = abs; g.ad = ad; g.abf = abf; g.y = y; g.ldy = (int)rows;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (e == hipSuccess && usec) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, nullptr); }
+    if (e == hipSuccess) e = launch_pf_gemm(g, EPI_STORE, nullptr);
+    if (e == hipSuccess && usec) {
+        (void)hipEventRecord(e1, nullptr);
+        (void)hipEventSynchronize(e1);
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        *usec = ms * 1e3;
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(aq); (void)hipFree(abs); (void)hipFree(ad); (void)hipFree(abf);
+    if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
+    return 0;
+}
+
+int32_t llmi_quantize_act(int32_t type, int64_t cols, const float* x, const float* nw, float eps, void* out) {
+    if (cols % 256) { set_err("cols must be a multiple of 256"); return -1; }
+    MVArgs a;
+    a.cols = (int)cols; a.x = x; a.nw = nw; a.eps = eps;
+    a.num = t_hook_numerics & NUMERICS_X86;
+    hipError_t e = launch_quant_dump(a, act_kind(type), out, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
+    return 0;
+}
+
+double llmi_bench_matvec_ex(int32_t type, const void* w, int32_t n_mats, int64_t rows, int64_t cols, const float* x, float* y,
+                            int32_t reps, int32_t mode) {
+    const int64_t lb = llmi_device_layout_bytes(type, rows, cols);
+    if (lb <= 0 || n_mats <= 0 || reps <= 0) { set_err("bad arguments"); return -1.0; }
+    const size_t stride = align_up((size_t)lb, 4096);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    hipDeviceProp_t prop;
+    (void)hipGetDeviceProperties(&prop, dev);
+    const int mb = std::max(64, prop.multiProcessorCount * wg_per_cu());
+    float* nw = nullptr;
+    StepState* st = nullptr;
+    // mode bit 5: gate+up SwiGLU launch (rows = both halves; RMSNorm on), bit 6: residual-add
+    // epilogue (ffn_down / attn_output)
+    const bool swiglu = mode & 32, add = mode & 64;
+    const bool norm = (mode & 1) || swiglu, logits = mode & 2, img = mode & 8;
+    if (norm) {
+        std::vector<float> ones((size_t)cols, 1.0f);
+        if (hipMalloc(&nw, (size_t)cols * 4) != hipSuccess) { set_err("out of device memory"); return -1.0; }
+        (void)hipMemcpy(nw, ones.data(), (size_t)cols * 4, hipMemcpyHostToDevice);
+    }
+    if (logits) {
+        if (hipMalloc(&st, sizeof(StepState)) != hipSuccess) { (void)hipFree(nw); set_err("out of device memory"); return -1.0; }
+        (void)hipMemset(st, 0, sizeof(StepState));
+    }
+    MVArgs a;
+    a.nseg = 1; a.cols = (int)cols; a.npairs = (int)((rows + 1) / 2); a.x = x; a.y = y;
+    a.nw = nw; a.eps = 1e-5f; a.xfirst = (mode & 4) ? 1 : (mode & 256) ? -1 : 0;  // mode bit 2: weights after x, bit 8: never
+    if (mode & 16) a.prio_alt = prop.multiProcessorCount;  // mode bit 4 (experiment builds): alternating priority
+    if (logits) { a.st = st; a.argmax = &st->key[0][0]; }
+    uint8_t* xq = nullptr;  // mode bit 3: timing with a pre-quantized activation image (zeros)
+    if (img) {
+        if (hipMalloc(&xq, (size_t)(cols / 256) * 304) != hipSuccess) { set_err("out of device memory"); return -1.0; }
+        (void)hipMemset(xq, 0, (size_t)(cols / 256) * 304);
+        a.xq = xq;
+    }
+    const int epi = logits ? EPI_LOGITS : swiglu ? EPI_SWIGLU : add ? EPI_ADD : EPI_STORE;
+    const size_t half = swiglu ? (size_t)llmi_device_layout_bytes(type, rows / 2, cols) : 0;
+    // one graph of n_mats launches (one per weight copy), replayed: no host launch cost
+    hipStream_t s = nullptr;
+    (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    hipGraph_t g = nullptr;
+    hipGraphExec_t ex = nullptr;
+    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    // mode bit 7: every launch reads copy 0 (its weights L2/MALL-hot from the launch before)
+    const size_t wstride = (mode & 128) ? 0 : stride;
+    for (int k = 0; ok && k < n_mats; ++k) {
+        if (swiglu) {
+            a.nseg = 2;
+            a.seg[0] = seg_at(type, (const uint8_t*)w + wstride * k, rows / 2, cols);
+            a.seg[1] = seg_at(type, (const uint8_t*)w + wstride * k + half, rows / 2, cols);
+        } else {
+            a.seg[0] = seg_at(type, (const uint8_t*)w + wstride * k, rows, cols);
+        }
+        ok = launch_matvec(a, epi, mb, s) == hipSuccess;
+    }
+    ok = (hipStreamEndCapture(s, &g) == hipSuccess) && ok && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
+    double res = -1.0;
+    const int nrep = std::max(1, reps / n_mats);
+    if (ok) {
+        hipEvent_t e0, e1;
+        (void)hipEventCreate(&e0);
+        (void)hipEventCreate(&e1);
+        (void)hipGraphLaunch(ex, s);  // warm-up (code, TLB)
+        (void)hipEventRecord(e0, s);
+        for (int r = 0; r < nrep; ++r) (void)hipGraphLaunch(ex, s);
+        (void)hipEventRecord(e1, s);
+        float ms = 0.f;
+        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
+            res = (double)ms * 1e3 / ((double)nrep * n_mats);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    } else {
+        set_err("llmi_bench_matvec: capture/launch failed");
+    }
+    if (ex) (void)hipGraphExecDestroy(ex);
+    if (g) (void)hipGraphDestroy(g);
+    (void)hipStreamDestroy(s);
+    (void)hipFree(nw);
+    (void)hipFree(st);
+    (void)hipFree(xq);
+    return res;
+}
+
+double llmi_bench_matvec(int32_t type, const void* w, int32_t n_mats, int64_t rows, int64_t cols, const float* x, float* y,
+                         int32_t reps) {
+    return llmi_bench_matvec_ex(type, w, n_mats, rows, cols, x, y, reps, 0);
+}
+
+double llmi_bench_stream(const void* dev, int32_t n_bufs, uint64_t stride, uint64_t bytes, int32_t reps, int32_t blocks) {
+    unsigned* out = nullptr;
+    if (hipMalloc(&out, 16) != hipSuccess) return -1.0;
+    for (int k = 0; k < n_bufs; ++k) (void)launch_stream_read((const uint8_t*)dev + stride * k, bytes, out, blocks, nullptr);
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    hipEventRecord(e0, nullptr);
+    for (int r = 0; r < reps; ++r) (void)launch_stream_read((const uint8_t*)dev + stride * (r % n_bufs), bytes, out, blocks, nullptr);
+    hipEventRecord(e1, nullptr);
+    hipEventSynchronize(e1);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, e0, e1);
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    (void)hipFree(out);
+    return (double)ms * 1e3 / reps;
+}
+
+}  // extern "C"
+
+// Attention microbenchmark (kernel level, no model): n_layers distinct KV caches of
+// n_ctx = round256(n_kv) positions (>= 512 MB in total, so replays stream them from HBM
+// like a decode step does), one launch per layer captured into a graph, `reps` graph
+// replays timed between two events.  Returns microseconds per launch (incl. the
+// dependent-launch gap), < 0 on error.  mode: attention path (0 auto, 1 fused, 2 split, 3 two-kernel).
+int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_kv, int32_t n_ctx, const float* q,
+                       const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || n_kv <= 0 ||
+        n_ctx < n_kv || n_ctx % 256 || !q || !kc || !vc || !out) {
+        set_err("llmi_attention: bad arguments");
+        return -1;
+    }
+    API_TRY
+    float* scores = nullptr;
+    StepState* st = nullptr;
+    if (hipMalloc(&scores, attn_scratch_floats(n_head, n_ctx) * 4) != hipSuccess || hipMalloc(&st, sizeof(StepState)) != hipSuccess) {
+        (void)hipFree(scores);
+        set_err("llmi_attention: out of device memory");
+        return -2;
+    }
+    StepState hs{};
+    hs.pos = n_kv - 1;
+    hs.pos_next = n_kv;
+    hs.seq = 1;
+    (void)hipMemcpy(st, &hs, sizeof(hs), hipMemcpyHostToDevice);
+    (void)hipMemset(scores, 0, attn_scratch_floats(n_head, n_ctx) * 4);
+    AttnArgs a;
+    a.q = q; a.kc = kc; a.vc = vc; a.scores = scores; a.out = out; a.st = st; a.n_ctx = n_ctx;
+    a.scale = 1.0f / sqrtf((float)head_dim);
+    a.tmax = scores + (size_t)n_head * n_ctx;
+    a.gran = (unsigned long long*)(scores + attn_gran_off(n_head, n_ctx));
+    a.fault = (unsigned*)(scores + attn_gran_off(n_head, n_ctx) + 2 * (size_t)n_head * kXAttnMaxKV);
+    a.num = t_hook_numerics & NUMERICS_X86;
+    a.fa = (t_hook_numerics & NUMERICS_FA) ? 1 : 0;
+    const int kv_bound = std::min(n_ctx, (n_kv + 255) / 256 * 256);
+    hipError_t e = launch_attention(a, n_head, n_head_kv, head_dim, kv_bound, nullptr, mode);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(scores);
+    (void)hipFree(st);
+    if (e != hipSuccess) { set_err(std::string("llmi_attention: ") + hip_err(e)); return -3; }
+    return 0;
+    API_CATCH(-5)
+}
+
+double llmi_pf_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
+                         const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode,
+                         int64_t scratch_bytes) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || T <= 0 ||
+        pos0 < 0 || n_ctx % 256 || pos0 + T > n_ctx || pos0 + T > kPfAttnMaxKV || mode < 0 || mode > 2 || !q || !kc ||
+        !vc || !out) {
+        set_err("llmi_pf_attention: bad arguments");
+        return -1;
+    }
+    API_TRY
+    PfAttn at;
+    at.q = q; at.out = out; at.ldq = n_head * head_dim; at.kc = kc; at.vc = vc;
+    at.n_ctx = n_ctx; at.pos0 = pos0; at.gqa = n_head / n_head_kv; at.max_kv = pos0 + T;
+    at.scale = 1.0f / sqrtf((float)head_dim);
+    float* wsc = nullptr;
+    if (mode == 0) {
+        size_t bytes = pf_fa_scratch_bytes(n_head, n_head_kv, head_dim, std::max(T, 512), n_ctx);
+        if (!bytes) { set_err("llmi_pf_attention: no tiled kernel for this head shape"); return -1; }
+        if (scratch_bytes > 0) bytes = (size_t)scratch_bytes;
+        if (hipMalloc(&wsc, bytes) != hipSuccess) { set_err("llmi_pf_attention: out of device memory"); return -2; }
+        at.wsc = wsc; at.wsc_bytes = bytes;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, nullptr);
+    hipError_t e = launch_pf_attn(at, n_head, head_dim, T, nullptr, mode);
+    (void)hipEventRecord(e1, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    float ms = 0.f;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipFree(wsc);
+    if (e != hipSuccess) { set_err(std::string("llmi_pf_attention: ") + hip_err(e)); return -3; }
+    return (double)ms * 1e3;
+    API_CATCH(-5)
+}
+
+double llmi_pf_attention_fa(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
+                            const float* q, const uint16_t* kc, const uint16_t* vc, float* out) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || n_head / n_head_kv > 32 ||
+        (head_dim != 64 && head_dim != 128) || T <= 0 || pos0 < 0 || n_ctx % 256 || pos0 + T > n_ctx ||
+        pos0 + T > kFaMaxKV || !q || !kc || !vc || !out) {
+        set_err("llmi_pf_attention_fa: bad arguments");
+        return -1;
+    }
+    API_TRY
+    PfAttn at;
+    at.q = q; at.out = out; at.ldq = n_head * head_dim; at.kc = kc; at.vc = vc;
+    at.n_ctx = n_ctx; at.pos0 = pos0; at.gqa = n_head / n_head_kv; at.max_kv = pos0 + T;
+    at.scale = 1.0f / sqrtf((float)head_dim);
+    at.num = t_hook_numerics & NUMERICS_X86;
+    at.fa = 1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, nullptr);
+    hipError_t e = launch_pf_attn(at, n_head, head_dim, T, nullptr);
+    (void)hipEventRecord(e1, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    float ms = 0.f;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (e != hipSuccess) { set_err(std::string("llmi_pf_attention_fa: ") + hip_err(e)); return -3; }
+    return (double)ms * 1e3;
+    API_CATCH(-5)
+}
+
+double llmi_bench_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_kv, int32_t mode, int32_t reps,
+                            uint64_t* trace_dev) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || n_kv <= 0 || reps <= 0) {
+        set_err("llmi_bench_attention: bad arguments");
+        return -1.0;
+    }
+    const int n_ctx = (n_kv + 255) / 256 * 256;
+    const size_t kv_layer = (size_t)n_head_kv * n_ctx * head_dim;  // elements per layer, K or V
+    const int nl = (int)std::max<size_t>(2, (size_t)(512u << 20) / (kv_layer * 4) + 1);
+    uint16_t *kc = nullptr, *vc = nullptr;
+    float *q = nullptr, *scores = nullptr, *out = nullptr;
+    StepState* st = nullptr;
+    auto cleanup = [&] {
+        (void)hipFree(kc); (void)hipFree(vc); (void)hipFree(q); (void)hipFree(scores); (void)hipFree(out); (void)hipFree(st);
+    };
+    if (hipMalloc(&kc, kv_layer * nl * 2) != hipSuccess || hipMalloc(&vc, kv_layer * nl * 2) != hipSuccess ||
+        hipMalloc(&q, (size_t)n_head * head_dim * 4) != hipSuccess ||
+        hipMalloc(&scores, attn_scratch_floats(n_head, n_ctx) * 4) != hipSuccess ||
+        hipMalloc(&out, (size_t)n_head * head_dim * 4) != hipSuccess || hipMalloc(&st, sizeof(StepState)) != hipSuccess) {
+        cleanup();
+        set_err("llmi_bench_attention: out of device memory");
+        return -1.0;
+    }
+    (void)hipMemset(kc, 0x3c, kv_layer * nl * 2);  // f16 0x3c3c ~ 1.06
+    (void)hipMemset(vc, 0x3c, kv_layer * nl * 2);
+    (void)hipMemset(q, 0, (size_t)n_head * head_dim * 4);
+    StepState hs{};
+    hs.pos = n_kv - 1;
+    hs.pos_next = n_kv;
+    (void)hipMemcpy(st, &hs, sizeof(hs), hipMemcpyHostToDevice);
+    hipStream_t s = nullptr;
+    (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    const int kv_bound = std::min(n_ctx, (n_kv + 255) / 256 * 256);
+    AttnArgs a;
+    a.q = q; a.scores = scores; a.out = out; a.st = st; a.n_ctx = n_ctx; a.scale = 1.0f / sqrtf((float)head_dim);
+    a.num = t_hook_numerics & NUMERICS_X86;
+    a.tmax = scores + (size_t)n_head * n_ctx;
+    a.gran = (unsigned long long*)(scores + attn_gran_off(n_head, n_ctx));
+    a.fault = (unsigned*)(scores + attn_gran_off(n_head, n_ctx) + 2 * (size_t)n_head * kXAttnMaxKV);
+    (void)hipMemset(scores, 0, attn_scratch_floats(n_head, n_ctx) * 4);
+    if (trace_dev) {  // one traced eager launch on a cold layer (LLMI_EXP_TRACE builds)
+        for (int l = 0; l + 1 < nl; ++l) {
+            a.kc = kc + (size_t)l * kv_layer;
+            a.vc = vc + (size_t)l * kv_layer;
+            a.layer = l % 255;
+            (void)launch_attention(a, n_head, n_head_kv, head_dim, kv_bound, s, mode);
+        }
+        a.kc = kc + (size_t)(nl - 1) * kv_layer;
+        a.vc = vc + (size_t)(nl - 1) * kv_layer;
+        a.layer = (nl - 1) % 255;
+        a.trace = (unsigned long long*)trace_dev;
+        const bool okt = launch_attention(a, n_head, n_head_kv, head_dim, kv_bound, s, mode) == hipSuccess &&
+                         hipStreamSynchronize(s) == hipSuccess;
+        (void)hipStreamDestroy(s);
+        cleanup();
+        return okt ? 0.0 : -1.0;
+    }
+    hipGraph_t g = nullptr;
+    hipGraphExec_t ex = nullptr;
+    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    // a new step sequence number per replay: k_attn_x's hand-off tags never repeat
+    ok = ok && launch_state_tick(st, s) == hipSuccess;
+    for (int l = 0; ok && l < nl; ++l) {
+        a.kc = kc + (size_t)l * kv_layer;
+        a.vc = vc + (size_t)l * kv_layer;
+        a.layer = l % 255;
+        ok = launch_attention(a, n_head, n_head_kv, head_dim, kv_bound, s, mode) == hipSuccess;
+    }
+    ok = (hipStreamEndCapture(s, &g) == hipSuccess) && ok && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
+    double res = -1.0;
+    if (ok) {
+        hipEvent_t e0, e1;
+        (void)hipEventCreate(&e0);
+        (void)hipEventCreate(&e1);
+        (void)hipGraphLaunch(ex, s);
+        (void)hipEventRecord(e0, s);
+        for (int r = 0; r < reps; ++r) (void)hipGraphLaunch(ex, s);
+        (void)hipEventRecord(e1, s);
+        float ms = 0.f;
+        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
+            res = (double)ms * 1e3 / ((double)reps * nl);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    } else {
+        set_err("llmi_bench_attention: capture/launch failed");
+    }
+    if (ex) (void)hipGraphExecDestroy(ex);
+    if (g) (void)hipGraphDestroy(g);
+    (void)hipStreamDestroy(s);
+    cleanup();
+    return res;
+}
+
+// Experiment hook (LLMI_EXP_TRACE builds): one STORE matvec launch with per-wave
+// s_memrealtime stamps {entry, after prologue, first pair done, exit, HW_ID, XCC<<32|pairs}
+// written to trace_dev[grid*waves*6]; returns the grid size, < 0 on error.
+int32_t llmi_trace_matvec(int32_t type, const void* w, int64_t rows, int64_t cols, const float* x, float* y, int32_t mode,
+                          uint64_t* trace_dev) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    hipDeviceProp_t prop;
+    (void)hipGetDeviceProperties(&prop, dev);
+    const int mb = std::max(64, prop.multiProcessorCount * wg_per_cu());
+    MVArgs a;
+    a.nseg = 1; a.cols = (int)cols; a.npairs = (int)((rows + 1) / 2); a.x = x; a.y = y;
+    a.seg[0] = seg_at(type, w, rows, cols);
+    a.trace = (unsigned long long*)trace_dev;
+    if (mode & 256) a.xfirst = -1;  // mode bit 8: weights issued before the activation arrives
+    uint8_t* xq = nullptr;  // mode bit 3: pre-quantized activation image (zeros)
+    if ((mode & 8) && hipMalloc(&xq, (size_t)(cols / 256) * 304) == hipSuccess) {
+        (void)hipMemset(xq, 0, (size_t)(cols / 256) * 304);
+        a.xq = xq;
+    }
+    const bool ok = launch_matvec(a, EPI_STORE, mb, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    (void)hipFree(xq);
+    if (!ok) {
+        set_err("llmi_trace_matvec: launch failed");
+        return -1;
+    }
+    return std::min(mb, (a.npairs + kMVWaves - 1) / kMVWaves);
+}

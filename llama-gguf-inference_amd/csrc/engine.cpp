@@ -910,15 +910,9 @@ static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std
 // rows with 4 working waves per workgroup, batch.hip mvn_work_waves).  A layer whose
 // ffn_gate and ffn_up differ in type has no batched step in any numerics (bstep_run's
 // error; llama_decode then steps such sequences one at a time)
-bool bstep_supported(const Model& m) {
-    (void)m;
-    return true;
-}
-
 bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err) {
     const HParams& hp = c.m->hp;
     if (nt < 1 || nt > kMaxBatch || c.n_seq < 2) { err = "batched step: 1..8 slots of a context with n_seq_max >= 2"; return false; }
-    if (!bstep_supported(*c.m)) { err = "batched step: not supported for this model"; return false; }
     for (const Layer& L : c.m->layers)
         if (L.wg.type != L.wu.type) { err = "batched step: ffn_gate / ffn_up of different types"; return false; }
     if (!balloc(c, err)) return false;

@@ -33,8 +33,9 @@ struct Layer {
 //     planes in the x86 byte order (common.h), fma chains per 4-byte lane, the x86
 //     attention (attn86.hip), ggml_v_expf softmax / SiLU, round-half-even q8_0
 //   + NUMERICS_FA (bit 1 of llama_model_params.numerics): decode attention in ggml's CPU
-//     flash-attention numerics (attnfa.hip) in the association of bit 0; such a model
-//     runs prompts as decode steps and batched sequences one after another
+//     flash-attention numerics (attnfa.hip) in the association of bit 0; a batched step
+//     runs that attention for all its slots in one launch, and prompts go through the
+//     batched prefill only with LLMI_FA_PREFILL=1 (else as decode steps)
 enum : int { NUMERICS_GENERIC = 0, NUMERICS_X86 = 1, NUMERICS_FA = 2 };
 
 struct Model {
@@ -178,7 +179,6 @@ double bytes_per_token(const Model& m, int n_kv);
 // batched prefill: can the model's layers run through the MFMA prefill path?  (flash-
 // attention numerics: only with LLMI_FA_PREFILL=1, read on every call)
 bool prefill_supported(const Model& m);
-bool bstep_supported(const Model& m);  // batched steps in this model's numerics (engine.cpp)
 // positions the batched prefill's attention reaches: the context when the tiled kernel
 // (k_pf_fa) takes the model's heads, else the LDS kernels' pf_max_kv()
 int prefill_max_kv(Context& c);
@@ -198,7 +198,5 @@ std::string hip_err(hipError_t e);
 // matvec grid cap = CUs x wg_per_cu() workgroups (env LLMI_WG_PER_CU, read when a context
 // is created; default 2: measured best on every config, profiles/r01/wg_sweep.md)
 int wg_per_cu();
-int64_t synth_write_gguf(const std::string& path, const std::string& preset, uint64_t seed, int n_layer, int n_vocab,
-                         int n_threads, std::string& err);
 
 }  // namespace llmi

@@ -66,4 +66,8 @@ private:
     std::map<std::string, size_t> index_;
 };
 
+// synth_writer.cpp: a synthetic GGUF of `preset`; bytes written, < 0 and err on failure
+int64_t synth_write_gguf(const std::string& path, const std::string& preset, uint64_t seed, int n_layer, int n_vocab,
+                         int n_threads, std::string& err);
+
 }  // namespace llmi
