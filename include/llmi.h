@@ -231,7 +231,8 @@ int32_t llmi_profile_kernels(struct llama_context* ctx, llama_token first, int32
  *                     xspin_limit 0: every such wait gives up at once; fault-path test)
  *   "numerics"        this thread's numerics for the kernel-level entry points below
  *                     (llmi_repack's byte order, llmi_matvec, llmi_quantize_act,
- *                     llmi_attention, llmi_pf_attention, llmi_pf_attention_fa):
+ *                     llmi_attention, llmi_battention, llmi_pf_attention,
+ *                     llmi_pf_attention_fa):
  *                     LLMI_NUMERICS_* */
 int32_t llmi_test_option(const char* name, int32_t value);
 /* Algorithmic bytes of one decode step at KV length n_kv (weights + one embedding row
@@ -349,6 +350,23 @@ double llmi_bench_stream(const void* dev, int32_t n_bufs, uint64_t stride, uint6
  * [n_head*head_dim].  n_ctx a multiple of 256.  0 on success. */
 int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_kv, int32_t n_ctx, const float* q,
                        const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode);
+/* The path launch_attention takes for this head shape at the KV bound kv_bound (a multiple
+ * of 256 in the engine) under `mode` (0 auto, 1..7 forced, LLMI_ATTN_MODE's numbering): 1
+ * fused, 2 split, 3 two-kernel, 4 exchange, 5 register-prefetched, 6 dim-split, 7
+ * long-context.  A forced mode outside its path's limits falls back, and this returns the
+ * path that runs.  Host only (no device call); < 0 for bad arguments. */
+int32_t llmi_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t kv_bound, int32_t mode);
+/* One batched-step attention (the batched step's launch_battention) of nt slots (1..8):
+ * slot t is a sequence of n_kv[t] live positions (n_kv: HOST array of nt lengths, each
+ * 1..n_ctx) with its own query q [nt][n_head*head_dim], caches kc [nt][n_head_kv][n_ctx]
+ * [head_dim] and vc [nt][n_head_kv][head_dim][n_ctx], output out [nt][n_head*head_dim],
+ * position and scratch, as the batched step sets them up; the KV bound is
+ * min(n_ctx, max n_kv rounded up to 256).  Path and slice count follow LLMI_BATTN_MODE /
+ * LLMI_BATTN_S (read per launch), the numerics this thread's "numerics" test option.
+ * n_ctx a multiple of 256.  Bad arguments are rejected before any device call.  0 on
+ * success. */
+int32_t llmi_battention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t nt, const int32_t* n_kv, int32_t n_ctx,
+                        const float* q, const uint16_t* kc, const uint16_t* vc, float* out);
 /* One batched-prefill attention (prefill_enqueue's launch_pf_attn) of T query tokens at
  * positions pos0..pos0+T-1 (q f32 [T][n_head*head_dim], roped; token t attends to
  * positions 0..pos0+t) over one layer's caches in the step's layout (as llmi_attention);

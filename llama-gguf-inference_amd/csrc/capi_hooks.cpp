@@ -459,6 +459,73 @@ int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
     API_CATCH(-5)
 }
 
+// The decode attention path launch_attention takes for this shape, KV bound and mode (host
+// only: no device call, so a test can ask on a machine without a GPU).
+int32_t llmi_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t kv_bound, int32_t mode) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || kv_bound <= 0 ||
+        mode < 0 || mode > 7) {
+        set_err("llmi_attn_path: bad arguments");
+        return -1;
+    }
+    return attn_path(n_head, n_head_kv, kv_bound, head_dim, mode);
+}
+
+// One batched-step attention (bstep_enqueue's launch_battention) of nt slots: slot t is one
+// sequence with its own caches, query, output, StepState (pos = n_kv[t] - 1) and scratch,
+// laid out as the batched step lays them out; the KV bound is the batch's (its longest slot).
+int32_t llmi_battention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t nt, const int32_t* n_kv, int32_t n_ctx,
+                        const float* q, const uint16_t* kc, const uint16_t* vc, float* out) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || nt < 1 ||
+        nt > kMaxBatch || !n_kv || n_ctx <= 0 || n_ctx % 256 || !q || !kc || !vc || !out) {
+        set_err("llmi_battention: bad arguments");
+        return -1;
+    }
+    int max_kv = 0;
+    for (int t = 0; t < nt; ++t) {
+        if (n_kv[t] <= 0 || n_kv[t] > n_ctx) { set_err("llmi_battention: n_kv outside 1..n_ctx"); return -1; }
+        max_kv = std::max(max_kv, n_kv[t]);
+    }
+    API_TRY
+    const size_t scr = attn_scratch_floats(n_head, n_ctx);
+    const size_t QD = (size_t)n_head * head_dim, kvl = (size_t)n_head_kv * n_ctx * head_dim;
+    float* scores = nullptr;
+    StepState* st = nullptr;
+    if (hipMalloc(&scores, (size_t)nt * scr * 4) != hipSuccess || hipMalloc(&st, (size_t)nt * sizeof(StepState)) != hipSuccess) {
+        (void)hipFree(scores);
+        set_err("llmi_battention: out of device memory");
+        return -2;
+    }
+    std::vector<StepState> hs((size_t)nt);
+    for (int t = 0; t < nt; ++t) {
+        hs[(size_t)t].pos = n_kv[t] - 1;
+        hs[(size_t)t].pos_next = n_kv[t];
+        hs[(size_t)t].seq = 1;
+    }
+    (void)hipMemcpy(st, hs.data(), (size_t)nt * sizeof(StepState), hipMemcpyHostToDevice);
+    (void)hipMemset(scores, 0, (size_t)nt * scr * 4);
+    BAttnArgs ba;
+    for (int t = 0; t < nt; ++t) {
+        AttnArgs& at = ba.a[t];
+        at.q = q + (size_t)t * QD; at.kc = kc + (size_t)t * kvl; at.vc = vc + (size_t)t * kvl;
+        at.scores = scores + (size_t)t * scr; at.tmax = at.scores + (size_t)n_head * n_ctx;
+        at.out = out + (size_t)t * QD; at.st = st + t; at.n_ctx = n_ctx;
+        at.scale = 1.0f / sqrtf((float)head_dim);
+        // (the batched step leaves the exchange path's granules unset: no batched path reads them)
+        at.gran = (unsigned long long*)(at.scores + attn_gran_off(n_head, n_ctx));
+        at.fault = (unsigned*)(at.scores + attn_gran_off(n_head, n_ctx) + 2 * (size_t)n_head * kXAttnMaxKV);
+        at.num = t_hook_numerics & NUMERICS_X86;
+        at.fa = (t_hook_numerics & NUMERICS_FA) ? 1 : 0;
+    }
+    const int kv_bound = std::min(n_ctx, (max_kv + 255) / 256 * 256);
+    hipError_t e = launch_battention(ba, nt, n_head, n_head_kv, head_dim, kv_bound, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(scores);
+    (void)hipFree(st);
+    if (e != hipSuccess) { set_err(std::string("llmi_battention: ") + hip_err(e)); return -3; }
+    return 0;
+    API_CATCH(-5)
+}
+
 double llmi_pf_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
                          const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode,
                          int64_t scratch_bytes) {
