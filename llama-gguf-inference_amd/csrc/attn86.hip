@@ -315,7 +315,7 @@ template <int D, int DS, int U>
 __global__ __launch_bounds__(kA86Threads) void k_a86_h(AttnArgs a, int n_head, int gq, int kvb, int stop) {
     a86_h_body<D, DS, U>(a, n_head, gq, kvb, stop);
 }
-// batched decode (batch.hip launch_battention): batch slot = blockIdx.y, its own sequence's
+// batched decode (battn.hip launch_battention): batch slot = blockIdx.y, its own sequence's
 // caches, q, output and position (kvb: the batch's common KV bound)
 template <int D, int DS, int U>
 __global__ __launch_bounds__(kA86Threads) void k_ba86_h(BAttnArgs b, int n_head, int gq, int kvb) {

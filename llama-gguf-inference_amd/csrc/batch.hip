@@ -9,8 +9,7 @@
 // its token's chains in ggml's generic order (mv_device.h) — so every sequence's results
 // are bit-identical to its own single-token decode.
 //
-// Attention runs the split kernels' bodies (mv_device.h) with a third grid dimension
-// over the batch slots, each slot reading its own sequence's KV cache.
+// The batched step's attention (launch_battention) is in battn.hip.
 #include "kernels.h"
 #include "mv_device.h"
 #include "pf_device.h"
@@ -252,18 +251,6 @@ __global__ __launch_bounds__(256) void k_bembed(BEmbArgs a) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e < a.cols) a.x[(size_t)s * a.cols + e] = dequant_elem(a.w, tok, e, a.cols);
 }
-
-template <int D, int G>
-__global__ __launch_bounds__(256) void k_battn_scores8(BAttnArgs b) {
-    const AttnArgs a = b.a[blockIdx.z];
-    attn_scores8_body<D, G>(a);
-}
-template <int D, int G>
-__global__ __launch_bounds__(512) void k_battn_pv16(BAttnArgs b, int kvb) {
-    const AttnArgs a = b.a[blockIdx.z];
-    attn_pv16_body<D, G>(a, kvb);
-}
-
 
 // ---- the batched matvec on the matrix cores ---------------------------------------------
 // k_bmm: workgroup = one ROW TILE of 16 rows (SWIGLU: 16 gate rows and the same 16 up
@@ -986,7 +973,6 @@ static int bmm_cap(const void* k, size_t lds) {
     return cap;
 }
 
-
 template <int T, int EPI, int X86>
 static hipError_t bmm_launch(const MVArgs& a, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s) {
     constexpr int NW = EPI == EPI_SWIGLU ? 2 : 1;
@@ -1093,106 +1079,6 @@ hipError_t launch_bembed(const BEmbArgs& a, hipStream_t s) {
     if (a.nt < 1 || a.nt > kMaxBatch) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bembed, dim3((a.cols + 255) / 256, a.nt), dim3(256), 0, s, a);
     return hipGetLastError();
-}
-
-// the single-sequence dim-split and long-context attention bodies (mv_device.h) with the
-// batch slot as the last grid dimension
-template <int D, int P, int S>
-__global__ __launch_bounds__(512) void k_battn_d(BAttnArgs b, int G, int HK, int kvb) {
-    attn_d_body<D, P, S>(b.a[blockIdx.y], G, HK, kvb, 1, 1);
-}
-template <int D, int G, int NP>
-__global__ __launch_bounds__(256) void k_battl_scores(BAttnArgs b) { attl_scores_body<D, G, NP>(b.a[blockIdx.z]); }
-__global__ __launch_bounds__(256) void k_battl_exp(BAttnArgs b, int n_head, int kvb) { attl_exp_body(b.a[blockIdx.z], n_head, kvb); }
-template <int D, int G>
-__global__ __launch_bounds__(512) void k_battl_pv(BAttnArgs b, int n_head, int kvb) { attl_pv_body<D, G>(b.a[blockIdx.z], n_head, kvb); }
-template <int D>
-__global__ __launch_bounds__(D) void k_battl_sum(BAttnArgs b, int n_head) { attl_sum_body<D>(b.a[blockIdx.z], n_head); }
-
-// batched attention path: dim split up to 1024 positions for up to 3 slots (8B bench:
-// 2 slots 940 vs 897 tok/s split, 4: 1335 vs 1341, 8: 1746 vs 1823 with 8 dim slices —
-// at 8 slots its redundant K reads cost more than the split path's second launch), and
-// for any slot count up to 512 positions with 1-2 slices (battn_slices), split while its
-// LDS fits up to 2048 (G <= 4) / 1024 positions, long-context beyond; LLMI_BATTN_MODE
-// (A/B only) forces 2 split, 6 dim split or 7 long-context
-// dim slices of the batched dim-split attention: the single-sequence choice (about 256
-// workgroups) is H * S * slots workgroups here, each re-reading its head's K rows; up to
-// 512 positions 2 slices for <= 4 slots and 1 beyond (8B, ~200 positions, 2/4/8 slots:
-// 721/960/1878 tok/s split or 8 slices -> 731/992/1945 with 2, 727/987/1963 with 1,
-// profiles/r05/batch/battn_slices.txt); LLMI_BATTN_S (A/B) forces 1, 2, 4 or 8
-static int battn_slices(int n_head, int head_dim, int kv_bound, int nt) {
-    if (const char* es = getenv("LLMI_BATTN_S")) {
-        const int v = atoi(es);
-        if ((v == 1 || v == 2 || v == 4 || v == 8) && head_dim / v >= 8) return v;
-    }
-    if (kv_bound <= 512 && nt >= 2) return nt > 4 ? 1 : 2;
-    return attn_d_slices(n_head, head_dim);
-}
-static int battn_path(int g, int n_head, int head_dim, int kv_bound, int nt) {
-    const char* e = getenv("LLMI_BATTN_MODE");
-    const int forced = e ? atoi(e) : 0;
-    const bool split_ok = (size_t)g * kv_bound * 4 <= kSplitAttnMaxLds;
-    const bool dim_ok = g <= 8 && kv_bound <= kDimAttnMaxKV && attn_d_slices(n_head, head_dim) >= 2;
-    if (forced == 2 && split_ok) return 2;
-    if (forced == 6 && dim_ok) return 6;
-    if (forced == 7 && g <= 8) return 7;
-    if (dim_ok && (nt <= 3 || kv_bound <= 512)) return 6;
-    if (split_ok && (g <= 4 ? kv_bound <= 2048 : kv_bound <= 1024)) return 2;
-    if (dim_ok) return 6;
-    return g <= 8 ? 7 : (split_ok ? 2 : 0);
-}
-
-hipError_t launch_battention(const BAttnArgs& b, int nt, int n_head, int n_head_kv, int head_dim, int kv_bound,
-                             hipStream_t s) {
-    if (nt < 1 || nt > kMaxBatch || n_head_kv <= 0 || n_head % n_head_kv) return hipErrorInvalidValue;
-    // the model's numerics (every slot's): flash attention, x86 association, else generic
-    if (b.a[0].fa) return launch_battention_fa(b, nt, n_head, n_head_kv, head_dim, kv_bound, s);
-    if (b.a[0].num) return launch_battention_x86(b, nt, n_head, n_head_kv, head_dim, kv_bound, s);
-    const int g = n_head / n_head_kv;
-    const int path = battn_path(g, n_head, head_dim, kv_bound, nt);
-    if (path == 6) {
-        const int p = kv_bound <= 64 ? 1 : kv_bound <= 128 ? 2 : kv_bound <= 256 ? 4 : kv_bound <= 512 ? 8
-                    : kv_bound <= 768 ? 12 : 16;
-        const int sd = battn_slices(n_head, head_dim, kv_bound, nt);
-#define LLMI_BATTD(D_, P_, S_) \
-        if (head_dim == D_ && p == P_ && sd == S_) { hipLaunchKernelGGL((k_battn_d<D_, P_, S_>), dim3(n_head * S_, nt), dim3(512), 0, s, b, g, n_head_kv, kv_bound); return hipGetLastError(); }
-#define LLMI_BATTD_P(D_, S_) LLMI_BATTD(D_, 1, S_) LLMI_BATTD(D_, 2, S_) LLMI_BATTD(D_, 4, S_) LLMI_BATTD(D_, 8, S_) LLMI_BATTD(D_, 12, S_) LLMI_BATTD(D_, 16, S_)
-        LLMI_BATTD_P(128, 1) LLMI_BATTD_P(128, 2) LLMI_BATTD_P(128, 4) LLMI_BATTD_P(128, 8)
-        LLMI_BATTD_P(64, 1) LLMI_BATTD_P(64, 2) LLMI_BATTD_P(64, 4) LLMI_BATTD_P(64, 8)
-#undef LLMI_BATTD_P
-#undef LLMI_BATTD
-        return hipErrorInvalidValue;
-    }
-    if (path == 7) {
-        const int ntile = (kv_bound + kLongTile - 1) / kLongTile;
-        const int np = kv_bound > 4096 ? 4 : 1;
-        const dim3 gs(n_head_kv, (kv_bound + 32 * np - 1) / (32 * np), nt);
-#define LLMI_BATTL(D_, G_)                                                                                        \
-        if (head_dim == D_ && g == G_) {                                                                          \
-            if (np == 4) hipLaunchKernelGGL((k_battl_scores<D_, G_, 4>), gs, dim3(256), 0, s, b);                 \
-            else hipLaunchKernelGGL((k_battl_scores<D_, G_, 1>), gs, dim3(256), 0, s, b);                         \
-            hipLaunchKernelGGL(k_battl_exp, dim3(n_head, ntile, nt), dim3(256), 0, s, b, n_head, kv_bound);       \
-            hipLaunchKernelGGL((k_battl_pv<D_, G_>), dim3(n_head_kv, ntile, nt), dim3(512), 0, s, b, n_head, kv_bound); \
-            hipLaunchKernelGGL((k_battl_sum<D_>), dim3(n_head, 1, nt), dim3(D_), 0, s, b, n_head);               \
-            return hipGetLastError();                                                                             \
-        }
-        LLMI_BATTL(128, 1) LLMI_BATTL(128, 2) LLMI_BATTL(128, 4) LLMI_BATTL(128, 8)
-        LLMI_BATTL(64, 1) LLMI_BATTL(64, 2) LLMI_BATTL(64, 4) LLMI_BATTL(64, 8)
-#undef LLMI_BATTL
-        return hipErrorInvalidValue;
-    }
-    if (path != 2) return hipErrorInvalidValue;
-    const size_t lds = (size_t)g * kv_bound * 4;
-#define LLMI_BATT(D_, G_)                                                                                    \
-    if (head_dim == D_ && g == G_) {                                                                         \
-        hipLaunchKernelGGL((k_battn_scores8<D_, G_>), dim3(n_head_kv, (kv_bound + 31) / 32, nt), dim3(256), 0, s, b); \
-        hipLaunchKernelGGL((k_battn_pv16<D_, G_>), dim3(n_head_kv, D_ / 16, nt), dim3(512), lds, s, b, kv_bound); \
-        return hipGetLastError();                                                                            \
-    }
-    LLMI_BATT(128, 1) LLMI_BATT(128, 2) LLMI_BATT(128, 4) LLMI_BATT(128, 8)
-    LLMI_BATT(64, 1) LLMI_BATT(64, 2) LLMI_BATT(64, 4) LLMI_BATT(64, 8)
-#undef LLMI_BATT
-    return hipErrorInvalidValue;
 }
 
 }  // namespace llmi

@@ -1,4 +1,4 @@
-// kernels.h — launch interface of the gfx950 decode kernels (kernels.hip).
+// kernels.h — launch interface of the gfx950 kernels (the .hip units of this directory).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,9 +17,9 @@ constexpr int kMVThreads = LLMI_MV_THREADS;  // matvec workgroup; each wave owns
 constexpr int kMVWaves = kMVThreads / 64;
 constexpr int kFusedAttnMaxKV = 8192;  // fused one-launch attention up to this KV bound (LDS scores)
 constexpr size_t kSplitAttnMaxLds = 128 * 1024;  // split attention: G * kv_bound f32 probabilities in LDS
-constexpr int kXAttnMaxKV = 1024;
+constexpr int kXAttnMaxKV = 1024;    // one-launch exchange attention (k_attn_x) up to this KV bound
 constexpr int kDimAttnMaxKV = 1024;  // dim-split one-launch attention (k_attn_d) up to this KV bound
-constexpr int kRegAttnMaxKV = 512;  // register-prefetched one-launch attention (k_attn_r) up to this KV bound  // one-launch exchange attention (k_attn_x) up to this KV bound
+constexpr int kRegAttnMaxKV = 512;   // register-prefetched one-launch attention (k_attn_r) up to this KV bound
 constexpr int kPfAttnMaxKV = 32768;  // batched-prefill attention: scores of one head in LDS
 // test options (llmi_test_option in capi.cpp): bit-identical path selection and lowered limits
 extern int g_pf_fa_noalloc, g_pf_gemm_ng, g_pf_qkv_merge, g_pf_xcd_map, g_pf_quant_bpc, g_pf_quant_split_below, g_pf_attn_simple, g_pf_attn_fa, g_pf_fa_cfg, g_pf_max_kv, g_xspin_limit, g_xtag_skew;
@@ -142,7 +142,7 @@ struct AttnArgs {
     int fa = 0;                           // 1: flash-attention numerics (attnfa.hip; num picks its association)
 };
 
-// Batched decode (batch.hip): up to kMaxBatch sequences advance one token per step.
+// Batched decode (batch.hip, battn.hip): up to kMaxBatch sequences advance one token per step.
 constexpr int kMaxBatch = 8;
 struct BAttnArgs {
     AttnArgs a[kMaxBatch];  // per batch slot (its sequence's caches, q, scratch, state)
@@ -249,13 +249,19 @@ hipError_t mv_qkv2_launch(const MVArgs& a, int split_tasks, dim3 grid, size_t ld
 
 // All launches are asynchronous on `stream` and graph-capturable (no allocation, no sync).
 hipError_t launch_matvec(const MVArgs& a, int epi, int max_blocks, hipStream_t stream);
-// attention path for a KV bound: 1 fused (one WG per head), 2 split (scores + PV over
-// (group, 16-dim slice) workgroups), 3 two-kernel long-context path, 4 one-launch
-// exchange (k_attn_x: scores tiles + granule hand-off + PV, kv_bound <= kXAttnMaxKV)
+// generic-numerics attention path for a KV bound, 1..7 (listed at the top of attn.hip)
 // mode: -1 the process setting (set_attn_mode, LLMI_ATTN_MODE at model load), 0 auto,
 // 1..7 one path (A/B and test hooks; a path whose limits the shape passes falls back)
 int attn_path(int n_head, int n_head_kv, int kv_bound, int head_dim, int mode = -1);
 int attn_d_slices(int n_head, int head_dim);
+// the batched step (battn.hip): path 2, 6, 7 or 0 (none applies), path 6's dim slices
+int battn_path(int g, int n_head, int head_dim, int kv_bound, int nt);
+int battn_slices(int n_head, int head_dim, int kv_bound, int nt);
+// paths 5 / 6: K passes of 64 positions for a KV bound, from 1, 2, 4, 8, 12, 16 up to cap
+int attn_passes(int kv_bound, int cap);
+// path 7: kLongTile tiles of the exp / PV grids, 32-position passes per scores workgroup, scores tiles
+struct LongGeo { int ntile, np, nscores; };
+LongGeo attn_long_geo(int kv_bound);
 // arm (or with nullptrs disarm) per-op kernel timing events for this thread's launches
 void set_launch_events(hipEvent_t start, hipEvent_t stop);
 void set_attn_mode(int mode);

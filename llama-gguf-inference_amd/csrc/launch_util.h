@@ -1,8 +1,10 @@
 // launch_util.h — host-side launch helper shared by the kernel translation units
-// (kernels.hip, the per-type matvec units mv_*.hip, prefill.hip).
+// (kernels.hip, attn.hip, attn86.hip, the per-type matvec units mv_*.hip, prefill.hip).
 #pragma once
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace llmi {
 
@@ -33,4 +35,20 @@ static void launch_k(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s,
     else hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
 }
 
+// Run-time values -> template arguments.  Of<As...>{v} is a value and the constants it may
+// equal; pick(f, of...) calls f(std::integral_constant<int, A>{}...) with the constant each
+// value equals and returns true, or returns false when a value is in no list.  The lists at
+// the call sites are therefore the whole set of instantiated kernels.
+template <int... As>
+struct Of { int v; };
+template <class F>
+static bool pick(F&& f) { return f(), true; }
+template <class F, int... As, class... Rest>
+static bool pick(F&& f, Of<As...> a, Rest... rest) {
+    return ((a.v == As && pick([&](auto... r) { f(std::integral_constant<int, As>{}, r...); }, rest...)) || ...);
+}
+using OfD = Of<128, 64>;     // head dims
+using OfG = Of<1, 2, 4, 8>;  // GQA groups of the kernels that take the group as a template argument
+
 }  // namespace llmi
+

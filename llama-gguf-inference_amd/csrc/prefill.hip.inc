@@ -1,5 +1,5 @@
 // prefill.hip.inc — batched prompt prefill on gfx950 MFMA (SURVEY.md §8f item 1, config C4).
-// Included at the end of kernels.hip: it shares that translation unit's device helpers
+// Included from prefill.hip: it shares mv_device.h's and pf_device.h's device helpers
 // (unit-major weight planes, the activation quantizer, fp16 conversions, DPP lanes).
 //
 // A prompt of T tokens runs through the same llm_build_llama graph as T decode steps,

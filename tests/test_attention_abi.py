@@ -1,5 +1,5 @@
 """The decode-attention hooks' C surface without a GPU: llmi_attn_path (host only) returns
-the path launch_attention takes, read off attn_path in csrc/kernels.hip, and
+the path launch_attention takes, read off attn_path in csrc/attn.hip, and
 llmi_battention rejects bad arguments before any device call."""
 from __future__ import annotations
 

@@ -66,7 +66,7 @@ def _slices(H, D):
 
 
 def expected_path(H, HK, D, kvb, mode):
-    """attn_path's limits (csrc/kernels.hip, kernels.h), restated."""
+    """attn_path's limits (csrc/attn.hip, kernels.h), restated."""
     G = H // HK
     split_ok, fused_ok = G * kvb * 4 <= 128 * 1024, kvb <= 8192
     inside = {0: False, 1: fused_ok, 2: split_ok, 3: True, 4: G <= 8 and kvb <= 1024, 5: kvb <= 512,
@@ -302,7 +302,7 @@ V_EXP_FA = -11  # flash-attention numerics accumulate V in f16 unnormalised: 410
 
 
 def _battn_path(H, HK, D, kvb, nt, forced):
-    """battn_path's choice (csrc/batch.hip), restated for the record this test prints."""
+    """battn_path's choice (csrc/attn.hip), restated for the record this test prints."""
     G = H // HK
     split_ok = G * kvb * 4 <= 128 * 1024
     dim_ok = G <= 8 and kvb <= 1024 and _slices(H, D) >= 2

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel ISA statistics of kernels.hip (device-only asm): cross-lane op counts,
+"""Per-kernel ISA statistics of one unit's device-only asm (kernels.hip, mv_*.hip, attn.hip): cross-lane op counts,
 vmcnt(0) waits, VGPRs, occupancy.  Usage: isa_stats.py k.s [name-filter]"""
 import re
 import sys
