@@ -230,7 +230,7 @@ int32_t llmi_profile_kernels(struct llama_context* ctx, llama_token first, int32
  *   "xtag_skew"       1: k_attn_x consumers wait for a tag no producer writes (with
  *                     xspin_limit 0: every such wait gives up at once; fault-path test)
  *   "numerics"        this thread's numerics for the kernel-level entry points below
- *                     (llmi_repack's byte order, llmi_matvec, llmi_quantize_act,
+ *                     (llmi_repack's byte order, llmi_matvec, llmi_bmv, llmi_quantize_act,
  *                     llmi_attention, llmi_battention, llmi_pf_attention,
  *                     llmi_pf_attention_fa):
  *                     LLMI_NUMERICS_* */
@@ -327,6 +327,20 @@ int32_t llmi_matvec(int32_t type, const void* w_dev, int64_t rows, int64_t cols,
  * n_tok llmi_matvec calls bit for bit.  usec (optional): device time of the GEMM launch. */
 int32_t llmi_pf_gemm(int32_t type, const void* w_dev, int64_t rows, int64_t cols, const float* x_dev,
                      const float* norm_w_dev, float eps, int32_t n_tok, float* y_dev, double* usec);
+/* One batched-decode matvec (the batched step's launch without a model): Y[t] = W .
+ * quantize(norm_w ? rmsnorm(x[t])*norm_w : x[t]) for nt (1..8) rows x[t] of `cols` floats,
+ * Y [nt][rows], stored; must equal nt llmi_matvec calls bit for bit.  kernel 0: k_mvn
+ * (launch_mvn; every type).  kernel 1: the matrix-core kernels (launch_pf_quant, then
+ * launch_bmm): k_bmd, or k_bmm under LLMI_BMM_DMA=0 (read per launch); K-quant types, rows
+ * a multiple of 16, x86 numerics on k_bmd only.  Never a fall-back from one kernel to the
+ * other: kernel 1 on arguments it does not take returns < 0.  x and y are copied through
+ * 8-row buffers of the hook's own (k_mvn pads nt to 1, 2, 4 or 8 tokens and touches the
+ * padded rows), so x_dev and y_dev need hold nt rows only.  The numerics are this thread's
+ * "numerics" test option.  Bad arguments (an unknown type, rows <= 0, cols no positive
+ * multiple of 256, nt outside 1..8, kernel outside 0..1, a null w/x/y) are rejected before
+ * any device call.  0 on success. */
+int32_t llmi_bmv(int32_t type, const void* w_dev, int64_t rows, int64_t cols, const float* x_dev,
+                 const float* norm_w_dev, float eps, int32_t nt, float* y_dev, int32_t kernel);
 /* the activation quantization the matvec prologue performs, written out in ggml block
  * form (block_q8_K for K-quant weight types, block_q8_0 for Q8_0) for bit-exact checks */
 int32_t llmi_quantize_act(int32_t type, int64_t cols, const float* x_dev, const float* norm_w_dev,

@@ -294,6 +294,66 @@ int32_t llmi_pf_gemm(int32_t type, const void* w, int64_t rows, int64_t cols, co
     return 0;
 }
 
+int32_t llmi_bmv(int32_t type, const void* w, int64_t rows, int64_t cols, const float* x, const float* nw, float eps,
+                 int32_t nt, float* y, int32_t kernel) {
+    if (!(type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0) || rows <= 0 || rows > INT32_MAX ||
+        cols <= 0 || cols > INT32_MAX || cols % 256 || nt < 1 || nt > kMaxBatch || kernel < 0 || kernel > 1 || !w || !x ||
+        !y) {
+        set_err("llmi_bmv: bad arguments");
+        return -1;
+    }
+    API_TRY
+    MVArgs a;
+    a.seg[0] = seg_at(type, w, rows, cols);
+    a.nseg = 1;
+    a.cols = (int)cols;
+    a.npairs = (int)((rows + 1) / 2);
+    a.nw = nw; a.eps = eps;
+    a.x_stride = (int)cols; a.y_stride = (int)rows;
+    a.num = t_hook_numerics & NUMERICS_X86;
+    // never a silent fall-back to k_mvn (host check, before any device call)
+    if (kernel == 1 && !bmm_ok(a, EPI_STORE)) {
+        set_err("llmi_bmv: the matrix-core kernels do not take these arguments (type, rows % 16, numerics, LLMI_BMM*)");
+        return -1;
+    }
+    // k_mvn pads nt to 1, 2, 4 or 8 tokens and reads and writes the padded rows: both
+    // sides go through kMaxBatch-row buffers of the hook's own, the x rows past nt zero
+    const size_t xb = (size_t)cols * 4, yb = (size_t)rows * 4, tpad = 64;
+    float *xp = nullptr, *yp = nullptr, *ad = nullptr;
+    void *aq = nullptr, *abf = nullptr;
+    int16_t* abs = nullptr;
+    hipError_t e = hipMalloc(&xp, kMaxBatch * xb);
+    if (e == hipSuccess) e = hipMalloc(&yp, kMaxBatch * yb);
+    if (e == hipSuccess) e = hipMemset(xp, 0, kMaxBatch * xb);
+    if (e == hipSuccess) e = hipMemset(yp, 0, kMaxBatch * yb);
+    if (e == hipSuccess) e = hipMemcpy(xp, x, (size_t)nt * xb, hipMemcpyDeviceToDevice);
+    a.x = xp; a.y = yp;
+    if (e == hipSuccess && kernel == 0) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        hipDeviceProp_t prop;
+        (void)hipGetDeviceProperties(&prop, dev);
+        e = launch_mvn(a, EPI_STORE, nt, std::max(64, prop.multiProcessorCount * wg_per_cu()), nullptr);
+    } else if (e == hipSuccess) {  // the scratch of llmi_pf_gemm (a superset of the batched step's 32 rows)
+        e = hipMalloc(&aq, tpad * cols * 2);
+        if (e == hipSuccess) e = hipMalloc(&abf, tpad * (cols / 256) * 64);
+        if (e == hipSuccess) e = hipMalloc(&abs, tpad * (cols / 16) * 2);
+        if (e == hipSuccess) e = hipMalloc(&ad, tpad * (cols / 32) * 4);
+        if (e == hipSuccess) e = hipMemset(aq, 0, tpad * cols * 2);
+        if (e == hipSuccess) e = hipMemset(abf, 0, tpad * (cols / 256) * 64);
+        if (e == hipSuccess) e = hipMemset(abs, 0, tpad * (cols / 16) * 2);
+        if (e == hipSuccess) e = hipMemset(ad, 0, tpad * (cols / 32) * 4);
+        if (e == hipSuccess) e = launch_pf_quant(xp, (int)cols, nw, eps, (int)cols, 0, nt, aq, abs, ad, abf, nullptr, a.num ? 1 : 0);
+        if (e == hipSuccess) e = launch_bmm(a, EPI_STORE, nt, aq, abf, ad, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(y, yp, (size_t)nt * yb, hipMemcpyDeviceToDevice);
+    (void)hipFree(xp); (void)hipFree(yp); (void)hipFree(aq); (void)hipFree(abf); (void)hipFree(abs); (void)hipFree(ad);
+    if (e != hipSuccess) { set_err(std::string("llmi_bmv: ") + hip_err(e)); return -2; }
+    return 0;
+    API_CATCH(-5)
+}
+
 int32_t llmi_quantize_act(int32_t type, int64_t cols, const float* x, const float* nw, float eps, void* out) {
     if (cols % 256) { set_err("cols must be a multiple of 256"); return -1; }
     MVArgs a;
