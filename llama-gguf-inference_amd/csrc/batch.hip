@@ -184,7 +184,8 @@ __global__ __launch_bounds__(kBT) void k_mvn(MVArgs A) {
             for (int t = 0; t < NT; ++t) {
                 float tm[9];
                 if constexpr (X86) unit_store_x86<T>(cur, smem + (size_t)t * img + (size_t)lu.u * kRec, F, r, ul, g.lr, g.R, lu.valid);
-                else unit_terms<T>(cur, smem + (size_t)t * img + (size_t)lu.u * kRec, tm);
+                // 8 tokens of Q5_K / Q6_K already spill at 256 VGPRs: no three-operand dots there
+                else unit_terms<T, !(NT == 8 && (T == T_Q5_K || T == T_Q6_K))>(cur, smem + (size_t)t * img + (size_t)lu.u * kRec, tm);
                 const MVArgs B = token_view(A, t, tseq[t]);
                 sub_finish<ACT, EPI, MVArgs, X86>(B, F, g, s, b, sg, tm, lu, r, ul, acc[t], vg[t], tpos[t], best[t]);
             }

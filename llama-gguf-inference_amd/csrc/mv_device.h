@@ -56,6 +56,16 @@ __device__ __forceinline__ uint32_t ldw4(const uint8_t* p) {
 __device__ __forceinline__ int dot4(uint32_t a, int b, int c) {
     return __builtin_amdgcn_sdot4((int)a, b, c, false);
 }
+// dot4 with a zero accumulator (every K-quant product: it is scaled before it is
+// accumulated).  dot4(a, b, 0) selects the two-address v_dot4c_i32_i8, whose accumulator is
+// its destination, and zeroes that register with a v_mov_b32 first: one extra VALU
+// instruction per dot (64 per Q4_K / Q5_K unit, 128 per Q6_K unit) plus the hazard s_nops
+// behind it.  The clamp flag forces the three-operand VOP3P v_dot4_i32_i8 with the inline
+// constant 0 as accumulator.  Exact: |dot4| <= 4 * 128 * 128 = 65536 when c = 0, so the
+// int32 clamp can never act.  Accumulating chains (Q8_0) stay on dot4: what v_dot4c is for.
+__device__ __forceinline__ int dot4z(uint32_t a, int b) {
+    return __builtin_amdgcn_sdot4((int)a, b, 0, true);
+}
 // ---- cross-lane exchange without LDS round trips (VALU latency): DPP within 16-lane
 // rows, v_permlane16/32_swap across rows / halves (gfx950).  xor_partner<o>(v) returns
 // v of lane L^o for o in {1,2,4,8,16,32}; for o = 4 / 8 the DPP row_half_mirror /
@@ -192,25 +202,42 @@ template <int ACT, int X86 = 0>
 __device__ __forceinline__ void quant_sub(const Lds& L, int cols, int sb, const float (&v)[16]) {
     int q[16];
     if constexpr (ACT == 0) {
-        // max |y| of the Q8_K block (order-free), then the SIGNED value ggml keeps: the
-        // first element (lowest index) whose |y| equals it ('if (ax > amax)' scan).  Key =
-        // (index within the block) * 2 + sign, minimised over the 16 lanes of the block.
-        float am = 0.f;
+        // The SIGNED value ggml keeps is the first element (lowest index) whose |y| is the
+        // block's largest ('if (ax > amax)' scan).  Two order-free maxima over the block give
+        // it without looking at indices: P = max y, N = max -y, max |y| = max(P, N) (>= 0: one
+        // of the two is), and the sign is that of the larger one.  Only P == N > 0 (+am and
+        // -am both present) needs the first index: then, behind a wave-uniform branch, key =
+        // (index within the block) * 2 + sign, minimised over the 16 lanes of the block --
+        // the right sign for every block, tied or not, so the lanes of the other blocks of the
+        // wave may take it along.
+        float P = v[0], N = -v[0];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) am = fmaxf(am, fabsf(v[j]));
-        am = fmaxf(am, xor_partner<1>(am));
-        am = fmaxf(am, xor_partner<2>(am));
-        am = fmaxf(am, xor_partner<4>(am));
-        am = fmaxf(am, xor_partner<8>(am));
-        int key = 0x7fffffff;
+        for (int j = 1; j < 16; ++j) {
+            P = fmaxf(P, v[j]);
+            N = fmaxf(N, -v[j]);
+        }
+        P = fmaxf(P, xor_partner<1>(P));
+        N = fmaxf(N, xor_partner<1>(N));
+        P = fmaxf(P, xor_partner<2>(P));
+        N = fmaxf(N, xor_partner<2>(N));
+        P = fmaxf(P, xor_partner<4>(P));
+        N = fmaxf(N, xor_partner<4>(N));
+        P = fmaxf(P, xor_partner<8>(P));
+        N = fmaxf(N, xor_partner<8>(N));
+        const float am = fmaxf(fmaxf(P, N), 0.f);
+        bool neg = N > P;
+        if (__any(P == N && am > 0.f)) {
+            int key = 0x7fffffff;
 #pragma unroll
-        for (int j = 15; j >= 0; --j)
-            key = fabsf(v[j]) == am ? (((sb & 15) * 16 + j) << 1) | (v[j] < 0.f ? 1 : 0) : key;
-        key = min(key, xor_partner_i<1>(key));
-        key = min(key, xor_partner_i<2>(key));
-        key = min(key, xor_partner_i<4>(key));
-        key = min(key, xor_partner_i<8>(key));
-        const float mv = (key & 1) ? -am : am;
+            for (int j = 15; j >= 0; --j)
+                key = fabsf(v[j]) == am ? (((sb & 15) * 16 + j) << 1) | (v[j] < 0.f ? 1 : 0) : key;
+            key = min(key, xor_partner_i<1>(key));
+            key = min(key, xor_partner_i<2>(key));
+            key = min(key, xor_partner_i<4>(key));
+            key = min(key, xor_partner_i<8>(key));
+            neg = key & 1;
+        }
+        const float mv = neg ? -am : am;
         float dval = 0.f;
         int bsum = 0;
         if (am == 0.f) {
@@ -525,8 +552,15 @@ __host__ __device__ constexpr int row_chains() { return ACT ? 1 : 9; }          
 // The unit's terms against activation record `rec` (kRec layout): K-quants tm[l] =
 // d*(float)aux32[l] (l < 8), tm[8] = -(dmin*(float)sumi) (Q6_K: +0, there is no min
 // chain and sumf starts at 0); Q8_0 tm[b] = (float)sumi_b * (d_w * d_a), b < 8.
-template <int T>
+template <int T, bool DZ = true>
 __device__ __forceinline__ void unit_terms(const UnitW<T>& w, const uint8_t* rec, float (&tm)[9]) {
+    // DZ = false keeps dot4(.., 0) (v_dot4c behind a zeroing move): for callers already at the
+    // 256-VGPR limit, where the three-operand form's separate destination adds spills
+    const auto dz = [](uint32_t a, int b) {
+        if constexpr (DZ) return dot4z(a, b);
+        else return dot4(a, b, 0);
+    };
+    (void)dz;
 #if defined(LLMI_EXP_NOVALU)
     // experiment builds only: the unit's integer work replaced by an XOR of its words (loads
     // kept live, results garbage) -- what the launch costs without the per-weight VALU
@@ -567,8 +601,8 @@ __device__ __forceinline__ void unit_terms(const UnitW<T>& w, const uint8_t* rec
                     h4 |= (l <= 4 ? hhi << (4 - l) : hhi >> (l - 4)) & 0x10101010u;
                 }
                 // |dot| <= 4*31*127, scales <= 63: exact 24-bit multiplies
-                t[l] = __mul24(slo, dot4(l4, alo[m], 0)) + t[l];
-                t[l] = __mul24(shi, dot4(h4, ahi[m], 0)) + t[l];
+                t[l] = __mul24(slo, dz(l4, alo[m])) + t[l];
+                t[l] = __mul24(shi, dz(h4, ahi[m])) + t[l];
             }
         }
         // sumi = sum_j m_j * (bs[2j] + bs[2j+1]): int16 pairs against (m_j, m_j)
@@ -607,10 +641,10 @@ __device__ __forceinline__ void unit_terms(const UnitW<T>& w, const uint8_t* rec
                 const uint32_t wh = ((q >> 4) & M4) | q6_hi_bytes((hh >> (2 * m)) & M2);
                 // |s| <= 2*32*127, |c| <= 128: exact in 24-bit multiplies
                 int a = t[4 * k + m];
-                a = __mul24(c0, dot4(wl, alo[m] & 0xffff, 0)) + a;
-                a = __mul24(c1, dot4(wl, alo[m] & (int)0xffff0000u, 0)) + a;
-                a = __mul24(c2, dot4(wh, ahi[m] & 0xffff, 0)) + a;
-                a = __mul24(c3, dot4(wh, ahi[m] & (int)0xffff0000u, 0)) + a;
+                a = __mul24(c0, dz(wl, alo[m] & 0xffff)) + a;
+                a = __mul24(c1, dz(wl, alo[m] & (int)0xffff0000u)) + a;
+                a = __mul24(c2, dz(wh, ahi[m] & 0xffff)) + a;
+                a = __mul24(c3, dz(wh, ahi[m] & (int)0xffff0000u)) + a;
                 t[4 * k + m] = a;
             }
         }
@@ -674,10 +708,10 @@ __device__ __forceinline__ void unit_terms_q6m(const UnitW<T_Q6_K>& w, const uin
             const uint32_t wl = (q & M4) | q6_hi_bytes((hl >> (2 * m)) & M2);
             const uint32_t wh = ((q >> 4) & M4) | q6_hi_bytes((hh >> (2 * m)) & M2);
             int a = t[4 * k + m];
-            a = __mul24(c0, dot4(wl, a0[m], 0)) + a;
-            a = __mul24(c1, dot4(wl, a1[m], 0)) + a;
-            a = __mul24(c2, dot4(wh, a2[m], 0)) + a;
-            a = __mul24(c3, dot4(wh, a3[m], 0)) + a;
+            a = __mul24(c0, dot4z(wl, a0[m])) + a;
+            a = __mul24(c1, dot4z(wl, a1[m])) + a;
+            a = __mul24(c2, dot4z(wh, a2[m])) + a;
+            a = __mul24(c3, dot4z(wh, a3[m])) + a;
             t[4 * k + m] = a;
         }
     }
@@ -783,8 +817,8 @@ __device__ __forceinline__ void unit_store_x86(const UnitW<T>& w, const uint8_t*
                 db[b] = dw * da;
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    s[bb][m] = (float)dot4(w.q[2 * b][m], a0[m], 0);
-                    s[bb][4 + m] = (float)dot4(w.q[2 * b + 1][m], a1[m], 0);
+                    s[bb][m] = (float)dot4z(w.q[2 * b][m], a0[m]);
+                    s[bb][4 + m] = (float)dot4z(w.q[2 * b + 1][m], a1[m]);
                 }
             }
             if (valid) {
@@ -825,8 +859,8 @@ __device__ __forceinline__ void unit_store_x86(const UnitW<T>& w, const uint8_t*
                         l4 |= (l <= 4 ? hlo << (4 - l) : hlo >> (l - 4)) & 0x10101010u;
                         h4 |= (l <= 4 ? hhi << (4 - l) : hhi >> (l - 4)) & 0x10101010u;
                     }
-                    t[l] = __mul24(slo, dot4(l4, alo[m], 0)) + t[l];
-                    t[l] = __mul24(shi, dot4(h4, ahi[m], 0)) + t[l];
+                    t[l] = __mul24(slo, dot4z(l4, alo[m])) + t[l];
+                    t[l] = __mul24(shi, dot4z(h4, ahi[m])) + t[l];
                 }
             }
             // bsum pairs (bs[2j], bs[2j+1]) against (m_j, m_j): prod[k] = pairs 2k, 2k+1
@@ -861,6 +895,9 @@ __device__ __forceinline__ void unit_store_x86(const UnitW<T>& w, const uint8_t*
                     const uint32_t wl = (q & M4) | q6_hi_bytes((hl >> (2 * m)) & M2);
                     const uint32_t wh = ((q >> 4) & M4) | q6_hi_bytes((hh >> (2 * m)) & M2);
                     int a = t[4 * k + m];
+                    // dot4(.., 0), not dot4z: with the three-operand form here the split
+                    // Q4_K / Q5_K + Q6_K QKV kernel (x86, fused norm) takes 169 VGPRs instead
+                    // of 168 and drops from 3 to 2 waves per SIMD
                     a = __mul24(clo, dot4(wl, alo[m], 0)) + a;
                     a = __mul24(chi, dot4(wh, ahi[m], 0)) + a;
                     t[4 * k + m] = a;
