@@ -180,7 +180,14 @@ bool model_load(const std::string& path, int device, bool vocab_only, bool no_up
         err = "GQA ratio unsupported";
         return false;
     }
-    if (hp.n_rot > D || hp.n_rot % 2) { err = "bad rope.dimension_count"; return false; }
+    if (hp.n_rot <= 0 || hp.n_rot > D || hp.n_rot % 2) { err = "bad rope.dimension_count"; return false; }
+    // scaled RoPE (linear, YaRN) is not implemented: refuse it, never decode it unscaled
+    const std::string rs_type = f.str("llama.rope.scaling.type", "none");
+    if (rs_type != "none") { err = "llama.rope.scaling.type '" + rs_type + "' not supported (RoPE is unscaled)"; return false; }
+    if (f.num("llama.rope.scaling.factor", 1.0) != 1.0) {
+        err = "llama.rope.scaling.factor other than 1 not supported (RoPE is unscaled)";
+        return false;
+    }
     if (E % 256 || hp.n_ff % 256) { err = "n_embd and n_ff must be multiples of 256"; return false; }
     auto chk = [&](const DevMat& m, int64_t rows, int64_t cols, const char* nm, bool quant) {
         if (m.rows != rows || m.cols != cols) { err = std::string(nm) + ": unexpected shape"; return false; }
@@ -192,7 +199,7 @@ bool model_load(const std::string& path, int device, bool vocab_only, bool no_up
         return true;
     };
     if (!chk(M.out_norm, 1, E, "output_norm", false)) return false;
-    if (M.tok_embd.cols != E) { err = "token_embd: unexpected shape"; return false; }
+    if (!chk(M.tok_embd, hp.n_vocab, E, "token_embd", true)) return false;
     if (!tied && !chk(M.output, hp.n_vocab, E, "output", true)) return false;
     for (const Layer& L : M.layers) {
         if (!chk(L.attn_norm, 1, E, "attn_norm", false) || !chk(L.ffn_norm, 1, E, "ffn_norm", false) ||
