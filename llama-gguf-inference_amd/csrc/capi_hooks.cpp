@@ -121,7 +121,14 @@ int32_t llmi_test_option(const char* name, int32_t value) {
         else if (value >= 0) { set_err("llmi_test_option: numerics must be 0..3"); return -1; }
         return old;
     }
+    if (!strcmp(name, "mv_unit_split")) {  // -1 auto (LLMI_MV_SPLIT), 0 off, 1 every launch that can, 2 / 3: kernels.hip
+        const int old = g_mv_unit_split;
+        if (value < -1 || value > 3) { set_err("llmi_test_option: mv_unit_split must be -1..3"); return -2; }
+        g_mv_unit_split = value;
+        return old;
+    }
     if (!strcmp(name, "pf_attn_simple")) opt = &g_pf_attn_simple;
+    else if (!strcmp(name, "mv_split_nt")) opt = &g_mv_split_nt;  // 0 auto (LLMI_MV_SPLIT_NT), 256, 512
     else if (!strcmp(name, "pf_fa_noalloc")) opt = &g_pf_fa_noalloc;
     else if (!strcmp(name, "pf_attn_fa")) opt = &g_pf_attn_fa;
     else if (!strcmp(name, "pf_gemm_ng")) opt = &g_pf_gemm_ng;

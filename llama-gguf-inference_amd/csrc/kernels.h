@@ -22,6 +22,7 @@ constexpr int kDimAttnMaxKV = 1024;  // dim-split one-launch attention (k_attn_d
 constexpr int kRegAttnMaxKV = 512;   // register-prefetched one-launch attention (k_attn_r) up to this KV bound
 constexpr int kPfAttnMaxKV = 32768;  // batched-prefill attention: scores of one head in LDS
 // test options (llmi_test_option in capi.cpp): bit-identical path selection and lowered limits
+extern int g_mv_unit_split, g_mv_split_nt;  // matvec unit split (kernels.hip LLMI_MV_SPLIT: -1 auto, 0 .. 3) and the workgroup threads of split launches (0 auto, 256, 512)
 extern int g_pf_fa_noalloc, g_pf_gemm_ng, g_pf_qkv_merge, g_pf_xcd_map, g_pf_quant_bpc, g_pf_quant_split_below, g_pf_attn_simple, g_pf_attn_fa, g_pf_fa_cfg, g_pf_max_kv, g_xspin_limit, g_xtag_skew;
 int pf_max_kv();  // llama_decode hands prompt runs reaching past this KV length to decode steps
 // scratch floats an attention context needs: scores [H][n_ctx] + tile maxima [H][n_ctx/32]
@@ -77,6 +78,12 @@ struct MVArgs {
     int lr = 0;                            // lanes per row (a multiple of 4)
     int rpt = 0;                           // rows per task R (SwiGLU: gate/up pairs)
     int ntasks = 0;
+    // split units (mv_device.h "Split units"; chosen by launch_matvec, k_matvec_split): us lanes
+    // share a unit (1 or 2), so lr = us x the units per sub-item.  A two-type launch gives its
+    // second type group a geometry of its own (us2 != 0): tasks [t2beg, t2end) of rpt2 rows,
+    // numbered from the launch's first row
+    int us = 1;
+    int us2 = 0, lr2 = 0, rpt2 = 0, t2beg = 0, t2end = 0;
     int split_tasks = 0;                   // two-type launches: tasks of the first type group ...
     int split_wgs = 0;                     // ... and the workgroups that run them
     int xfirst = 0;                        // experiment: 1 multi-round launches also wait for x before weights, -1 none does
@@ -246,6 +253,14 @@ template <int ACT, bool NORM, int T, int X86>
 hipError_t mv_dispatch_epi(const MVArgs& a, int epi, dim3 grid, size_t lds, hipStream_t s);
 template <bool NORM, int T, int T2, int X86>
 hipError_t mv_qkv2_launch(const MVArgs& a, int split_tasks, dim3 grid, size_t lds, hipStream_t s);
+// split-unit launchers (k_matvec_split; instantiated in mv_split.hip): a single-type launch
+// with every unit split (a.us == 2; epi STORE, ADD or QKV), and the Q4_K + Q6_K QKV launch
+// whose Q6_K group is split (a.us2 == 2) and whose Q4_K group is (US == 2) or is not.
+// nt: workgroup threads, 256 or 512.
+template <bool NORM, int T, int X86>
+hipError_t mv_split_launch(const MVArgs& a, int epi, int nt, hipStream_t s);
+template <int X86, int US>
+hipError_t mv_split_qkv2_launch(const MVArgs& a, int nt, hipStream_t s);
 
 // All launches are asynchronous on `stream` and graph-capturable (no allocation, no sync).
 hipError_t launch_matvec(const MVArgs& a, int epi, int max_blocks, hipStream_t stream);

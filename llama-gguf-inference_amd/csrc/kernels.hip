@@ -30,6 +30,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 #include <hip/hip_runtime.h>
 
@@ -337,16 +338,19 @@ static hipError_t mv_dispatch_type(const MVArgs& a, int epi, dim3 grid, size_t l
 // Row-task geometry (mv_device.h "Row tasks"): Lr lanes per row = U rounded up to a
 // multiple of 4, at most 64 (QKV: 32, so that a task holds RoPE pairs); R = 64 / Lr
 // rounded down to a power of two, halved until every segment starts on a task boundary.
-bool mv_geometry(MVArgs& a, int epi) {
-    if (a.nseg < 1 || a.cols < 256 || a.cols % 256) return false;
-    const int U = a.cols >> 8, lmax = epi == EPI_QKV ? 32 : 64;
-    static const int lr_cap = [] {  // A/B knob: cap on lanes per row (more rows per task)
+// With us = 2 lanes per unit (mv_device.h "Split units") the same holds for the units: at
+// most 32 (QKV: 16) units per sub-item, Lr = twice that, R = 64 / Lr: a 4096-column row is
+// 32 lanes, two rows per task, twice the tasks.
+static void mv_geo_lanes(const MVArgs& a, int epi, int us, int& lr, int& R) {
+    const int U = a.cols >> 8, lmax = (epi == EPI_QKV ? 32 : 64) / us;
+    static const int lr_cap = [] {  // A/B knob: cap on units per row (more rows per task)
         const char* e = getenv("LLMI_MV_LR");
         return e ? atoi(e) : 64;
     }();
-    int lr = (std::min(std::min(U, lmax), lr_cap) + 3) & ~3;
-    lr = std::min(std::max(lr, 4), lmax);
-    int R = 1;
+    int lu = (std::min(std::min(U, lmax), lr_cap) + 3) & ~3;
+    lu = std::min(std::max(lu, 4), lmax);
+    lr = lu * us;
+    R = 1;
     while (2 * R * lr <= 64) R *= 2;
     auto aligned = [&](int r) {
         for (int i = 1; i < a.nseg; ++i)
@@ -355,7 +359,17 @@ bool mv_geometry(MVArgs& a, int epi) {
     };
     if (epi != EPI_SWIGLU)
         while (R > 1 && !aligned(R)) R >>= 1;
+}
+bool mv_geometry(MVArgs& a, int epi) {
+    if (a.nseg < 1 || a.cols < 256 || a.cols % 256 || (a.us != 1 && a.us != 2)) return false;
+    int lr, R;
+    mv_geo_lanes(a, epi, a.us, lr, R);
     if (epi == EPI_QKV && R < 2) return false;
+    if (a.us2) {  // the second type group's own geometry
+        if (a.us2 != 1 && a.us2 != 2) return false;
+        mv_geo_lanes(a, epi, a.us2, a.lr2, a.rpt2);
+        if (epi == EPI_QKV && a.rpt2 < 2) return false;
+    }
     int rows;
     if (epi == EPI_SWIGLU) {
         if (a.nseg != 2 || a.seg[0].rows != a.seg[1].rows) return false;
@@ -380,11 +394,102 @@ static int mv_fw() {
     return v;
 }
 
+// Split units (mv_device.h "Split units"): which launches run with two lanes per unit.
+// LLMI_MV_SPLIT = auto (default) | 0 | 1 | 2 | 3, or the test option mv_unit_split (-1 auto):
+//   1  every launch that can: K-quant STORE / ADD / QKV launches of Q4_K or Q6_K alone, and
+//      both groups of a Q4_K + Q6_K QKV launch
+//   2  only the Q6_K group of a Q4_K + Q6_K QKV launch (the slower group: 2.4 x the
+//      instructions of a Q4_K wave, dispatched last)
+//   3  2, and the single-type launches that are single-round today (unsplit tasks <= the
+//      waves the grid holds: attn_output, an all-Q4_K QKV; not ffn_down)
+//   auto = 3: every class's own kernel time came down (profiles/mv_split).
+// LLMI_MV_SPLIT_NT = 256 (default) | 512 (test option mv_split_nt): the workgroup of a split
+// launch; two 4-wave workgroups per CU measured faster than one of 8 waves on the all-Q4_K QKV
+// (8.24 vs 9.17 us) and the same on the other two classes.
+// Like every launch knob neither changes a result.
+int g_mv_unit_split = -1;
+int g_mv_split_nt = 0;
+static int mv_split_mode() {
+    static const int env = [] {
+        const char* e = getenv("LLMI_MV_SPLIT");
+        return e && strcmp(e, "auto") ? atoi(e) : -1;
+    }();
+    const int m = g_mv_unit_split >= 0 ? g_mv_unit_split : env;
+    return m < 0 || m > 3 ? 3 : m;
+}
+static int mv_split_nt() {
+    static const int env = [] {
+        const char* e = getenv("LLMI_MV_SPLIT_NT");
+        return e ? atoi(e) : 0;
+    }();
+    const int v = g_mv_split_nt ? g_mv_split_nt : env;
+    return v == 256 || v == 512 ? v : 256;
+}
+// Sets a.us / a.us2 for the launch; returns 0 (no split), 1 (single type), 2 (two groups)
+static int mv_split_plan(MVArgs& a, int epi, int max_blocks) {
+    static const bool qkv2 = !getenv("LLMI_NO_QKV2");
+    const int mode = mv_split_mode();
+    if (mode == 0 || !(epi == EPI_STORE || epi == EPI_ADD || epi == EPI_QKV)) return 0;
+    if (epi == EPI_QKV && !a.nw) return 0;
+    int t1 = a.seg[0].type, t2 = -1;
+    for (int i = 1; i < a.nseg; ++i) {
+        if (a.seg[i].type == (t2 < 0 ? t1 : t2)) continue;
+        if (t2 >= 0) return 0;  // a third group
+        t2 = a.seg[i].type;
+    }
+    const int waves = max_blocks * kMVWaves;  // what the grid of 4-wave workgroups holds
+    MVArgs g = a;
+    if (t2 < 0) {
+        if ((t1 != T_Q4_K && t1 != T_Q6_K) || mode == 2) return 0;
+        if (!mv_geometry(g, epi)) return 0;
+        if (mode == 3 && g.ntasks > waves) return 0;  // (unsplit: not single-round today)
+        g.us = 2;
+        if (!mv_geometry(g, epi)) return 0;
+        a.us = 2;
+        return 1;
+    }
+    if (epi != EPI_QKV || !qkv2 || t1 != T_Q4_K || t2 != T_Q6_K || a.cols > 16 * kMVThreads) return 0;
+    a.us = mode == 1 ? 2 : 1;
+    a.us2 = 2;
+    return 2;
+}
+
 hipError_t launch_matvec(const MVArgs& a0, int epi, int max_blocks, hipStream_t s) {
     if (a0.nseg < 1 || a0.cols <= 0 || a0.cols % 256) return hipErrorInvalidValue;
     MVArgs a = a0;
     a.fw = mv_fw();
+    a.us = 1;
+    a.us2 = 0;
+    const int split = act_kind(a.seg[0].type) == 0 ? mv_split_plan(a, epi, max_blocks) : 0;
     if (!mv_geometry(a, epi)) return hipErrorInvalidValue;
+    if (split) {
+        for (int i = 0; i < a.nseg; ++i)
+            if (act_kind(a.seg[i].type) != 0 || (a.seg[i].x86 != 0) != (a.num != 0)) return hipErrorInvalidValue;
+        const int nt = mv_split_nt();
+        if (split == 1) {
+            const int t = a.seg[0].type;
+#define LLMI_SPLIT1(N_, T_, X_) return mv_split_launch<N_, T_, X_>(a, epi, nt, s)
+            if (a.nw) {
+                if (t == T_Q4_K) { if (a.num) LLMI_SPLIT1(true, T_Q4_K, 1); else LLMI_SPLIT1(true, T_Q4_K, 0); }
+                else { if (a.num) LLMI_SPLIT1(true, T_Q6_K, 1); else LLMI_SPLIT1(true, T_Q6_K, 0); }
+            } else {
+                if (t == T_Q4_K) { if (a.num) LLMI_SPLIT1(false, T_Q4_K, 1); else LLMI_SPLIT1(false, T_Q4_K, 0); }
+                else { if (a.num) LLMI_SPLIT1(false, T_Q6_K, 1); else LLMI_SPLIT1(false, T_Q6_K, 0); }
+            }
+#undef LLMI_SPLIT1
+        }
+        // two groups: the Q6_K rows start at the first Q6_K segment (a task boundary of both geometries)
+        int split_row = 0;
+        for (int i = a.nseg - 1; i >= 1; --i)
+            if (a.seg[i].type == T_Q6_K) split_row = a.seg[i].row0 - a.seg[0].row0;
+        const int rows = a.seg[a.nseg - 1].row0 + a.seg[a.nseg - 1].rows - a.seg[0].row0;
+        if (split_row <= 0 || split_row % a.rpt || split_row % a.rpt2) return hipErrorInvalidValue;
+        a.split_tasks = split_row / a.rpt;
+        a.t2beg = split_row / a.rpt2;
+        a.t2end = (rows + a.rpt2 - 1) / a.rpt2;
+        if (a.us == 2) return a.num ? mv_split_qkv2_launch<1, 2>(a, nt, s) : mv_split_qkv2_launch<0, 2>(a, nt, s);
+        return a.num ? mv_split_qkv2_launch<1, 1>(a, nt, s) : mv_split_qkv2_launch<0, 1>(a, nt, s);
+    }
     const int act = act_kind(a.seg[0].type);
     for (int i = 1; i < a.nseg; ++i)
         if (act_kind(a.seg[i].type) != act) return hipErrorInvalidValue;

@@ -1381,6 +1381,223 @@ __device__ __forceinline__ void task_any(const MA& A, const Lds& L, float* F, co
     }
 }
 
+// ----------------------------------------------------------------------------------
+// Split units (MVArgs::us == 2; k_matvec_split, mv_kernels.h).  Lanes 2k and 2k + 1 of a
+// row share unit k: the even lane takes parts 0-3 (chunks 0, 1) and the odd lane parts 4-7
+// (chunks 2, 3), each with its half of the activation record, so a short launch has twice
+// the waves and each wave half the dependent chain.  A lane forms the PARTIAL integer sums
+// of its four parts -- the eight t[l] and, Q4_K, its half of the min sum (sub-blocks 4 half
+// .. 4 half + 3; the x86 form: prod[2 half], prod[2 half + 1]) -- and the partner's are
+// added by one DPP neighbour swap per value.  Integer sums are exact in any grouping and a
+// partial is no larger than the whole (every |dot4|, 24-bit multiply and int32 bound above
+// holds for it), so the even lane then forms exactly the fp32 terms of the unsplit unit and
+// stores them; the odd lane stores nothing.  The fold buffer, the fold lanes, row_final and
+// the epilogues stay indexed by (row, chain, unit): TaskGeo::lr is the UNITS per sub-item
+// here (MVArgs::lr / 2), and every fp32 operation of a row runs as in the unsplit geometry.
+// Q4_K and Q6_K (the types of the single-round launches of the flagship); Q5_K stays unsplit.
+// ----------------------------------------------------------------------------------
+// geometry of a split group: `lanes` lanes per row, two per unit, R rows per task
+__host__ __device__ inline TaskGeo task_geo_split(const MVArgs& A, int lanes, int R) {
+    TaskGeo g;
+    g.lr = lanes >> 1;
+    g.R = R;
+    g.U = A.cols >> 8;
+    g.nj = (g.U + g.lr - 1) / g.lr;
+    return g;
+}
+template <int T>
+struct HalfW {
+    u32x4 q[4];   // parts 4 half .. 4 half + 3
+    u32x4 s;      // Q4_K: the whole header (one line, read by both lanes); Q6_K: .x, .y the
+                  // scale dwords of chunks 2 half, 2 half + 1
+    u32x4 h[2];   // Q6_K: the 2-bit highs of chunks 2 half, 2 half + 1
+    uint32_t d;   // Q6_K fp16 d
+};
+template <int T>
+__device__ __forceinline__ HalfW<T> load_half(const Seg& sg, uint32_t row, uint32_t u, uint32_t U, uint32_t half) {
+    static_assert(T == T_Q4_K || T == T_Q6_K, "split units: Q4_K and Q6_K");
+    HalfW<T> w;
+    const uint32_t P = (U * 16) << sg.rgs, ru = row * U + u;
+    const uint32_t oa = piece_off(row, 0, u, U, 8, sg.rgs) + 4 * half * P;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) w.q[p] = ldw(sg.a + oa + (uint32_t)p * P);
+    if constexpr (T == T_Q4_K) {
+        w.s = ldw(sg.s + ru * 16);
+        w.d = 0;
+    } else {
+        const u32x2 s2 = ldw8(sg.s + ru * 16 + 8 * half);
+        w.s = u32x4{s2.x, s2.y, 0u, 0u};
+        const uint32_t oh = piece_off(row, 0, u, U, 4, sg.rgs) + 2 * half * P;
+        w.h[0] = ldw(sg.h + oh);
+        w.h[1] = ldw(sg.h + oh + P);
+        w.d = *(const uint16_t*)(sg.d + ru * 2);
+    }
+    return w;
+}
+// the eight lane sums of both halves joined: t[l] of the whole unit in both lanes
+__device__ __forceinline__ void join_halves(int (&t)[8]) {
+#pragma unroll
+    for (int l = 0; l < 8; ++l) t[l] += xor_partner_i<1>(t[l]);
+}
+// Q4_K: partial t[l] of parts 4 half .. + 3 and the min pair sums pr[0], pr[1] of sub-block
+// pairs (4 half, 4 half + 1), (4 half + 2, 4 half + 3) (generic and x86 layouts alike, as
+// in unit_terms / unit_store_x86)
+__device__ __forceinline__ void half_ints_q4(const HalfW<T_Q4_K>& w, const uint8_t* rec, uint32_t half, int (&t)[8],
+                                             int (&pr)[2]) {
+    u32x2 sc, mn;
+    scales_mins(w.s.y, w.s.z, w.s.w, sc, mn);
+    const uint32_t sw = half ? sc.y : sc.x, mw = half ? mn.y : mn.x;
+    const uint8_t* a = rec + 128 * half;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) t[l] = 0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int c = p >> 1, k = p & 1;
+        const int slo = (int)((sw >> (16 * c)) & 0xffu), shi = (int)((sw >> (16 * c + 8)) & 0xffu);
+        const i32x4 alo = *(const i32x4*)(a + 32 * p), ahi = *(const i32x4*)(a + 32 * p + 16);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int l = 4 * k + m;
+            const uint32_t l4 = w.q[p][m] & M4, h4 = (w.q[p][m] >> 4) & M4;
+            t[l] = __mul24(slo, dot4z(l4, alo[m])) + t[l];
+            t[l] = __mul24(shi, dot4z(h4, ahi[m])) + t[l];
+        }
+    }
+    const i32x4 bs = *(const i32x4*)(rec + kRecBs + 16 * half);
+    pr[0] = 0;
+    pr[1] = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t sel = 0x0c000c00u | (uint32_t)j * 0x00010001u;
+        const uint32_t mm = __builtin_amdgcn_perm(0u, mw, sel);
+        const int bp = bs[j];  // (a copy: __builtin_bit_cast of the vector element itself reads element 0)
+        pr[j >> 1] = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, bp), __builtin_bit_cast(short2_t, mm), pr[j >> 1], false);
+    }
+}
+// Q6_K, generic layout: partial t[l] of parts 4 half .. + 3.  MASKED: `a` is the half's 256
+// bytes of the masked record (q6_masks_build), else its 128 bytes of the plain record.
+template <bool MASKED>
+__device__ __forceinline__ void half_ints_q6(const HalfW<T_Q6_K>& w, const uint8_t* a, int (&t)[8]) {
+#pragma unroll
+    for (int l = 0; l < 8; ++l) t[l] = 0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int c = p >> 1, k = p & 1;
+        const uint32_t s4 = c ? w.s.y : w.s.x;
+        const int c0 = (int)(int8_t)(s4 & 0xff), c1 = (int)(int8_t)((s4 >> 8) & 0xff),
+                  c2 = (int)(int8_t)((s4 >> 16) & 0xff), c3 = (int)(int8_t)(s4 >> 24);
+        i32x4 a0, a1, a2, a3;
+        if constexpr (MASKED) {
+            a0 = *(const i32x4*)(a + 64 * p), a1 = *(const i32x4*)(a + 64 * p + 16);
+            a2 = *(const i32x4*)(a + 64 * p + 32), a3 = *(const i32x4*)(a + 64 * p + 48);
+        } else {
+            const i32x4 alo = *(const i32x4*)(a + 32 * p), ahi = *(const i32x4*)(a + 32 * p + 16);
+            a0 = alo & 0xffff, a1 = alo & (int)0xffff0000u, a2 = ahi & 0xffff, a3 = ahi & (int)0xffff0000u;
+        }
+        const uint32_t hl = w.h[c][k], hh = w.h[c][2 + k];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t q = w.q[p][m];
+            const uint32_t wl = (q & M4) | q6_hi_bytes((hl >> (2 * m)) & M2);
+            const uint32_t wh = ((q >> 4) & M4) | q6_hi_bytes((hh >> (2 * m)) & M2);
+            int v = t[4 * k + m];
+            v = __mul24(c0, dot4z(wl, a0[m])) + v;
+            v = __mul24(c1, dot4z(wl, a1[m])) + v;
+            v = __mul24(c2, dot4z(wh, a2[m])) + v;
+            v = __mul24(c3, dot4z(wh, a3[m])) + v;
+            t[4 * k + m] = v;
+        }
+    }
+}
+// Q6_K, x86 layout (a dword = 4 consecutive elements of one sub-block, one scale)
+__device__ __forceinline__ void half_ints_q6_x86(const HalfW<T_Q6_K>& w, const uint8_t* a, int (&t)[8]) {
+#pragma unroll
+    for (int l = 0; l < 8; ++l) t[l] = 0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int c = p >> 1, k = p & 1;
+        const uint32_t s4 = c ? w.s.y : w.s.x;
+        const int clo = (int)(int8_t)((s4 >> (8 * k)) & 0xff), chi = (int)(int8_t)((s4 >> (8 * (2 + k))) & 0xff);
+        const i32x4 alo = *(const i32x4*)(a + 32 * p), ahi = *(const i32x4*)(a + 32 * p + 16);
+        const uint32_t hl = w.h[c][k], hh = w.h[c][2 + k];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t q = w.q[p][m];
+            const uint32_t wl = (q & M4) | q6_hi_bytes((hl >> (2 * m)) & M2);
+            const uint32_t wh = ((q >> 4) & M4) | q6_hi_bytes((hh >> (2 * m)) & M2);
+            int v = t[4 * k + m];
+            v = __mul24(clo, dot4z(wl, alo[m])) + v;
+            v = __mul24(chi, dot4z(wh, ahi[m])) + v;
+            t[4 * k + m] = v;
+        }
+    }
+}
+// The lane's half of unit `rec` (generic order): the whole unit's terms tm as unit_terms /
+// unit_terms_q6m form them, valid in both lanes of the pair.  q6m: the unit's masked record
+// (Q6_K with MASKED).
+template <int T, bool MASKED>
+__device__ __forceinline__ void half_terms(const HalfW<T>& w, const uint8_t* rec, const uint8_t* q6m, uint32_t half,
+                                           float (&tm)[9]) {
+    int t[8];
+    const float da = *(const float*)(rec + kRecD);
+    if constexpr (T == T_Q4_K) {
+        int pr[2];
+        half_ints_q4(w, rec, half, t, pr);
+        join_halves(t);
+        int sumi = pr[0] + pr[1];
+        sumi += xor_partner_i<1>(sumi);
+        const float d = h2f(w.s.x) * da, dm = h2f(w.s.x >> 16) * da;
+#pragma unroll
+        for (int l = 0; l < 8; ++l) tm[l] = d * (float)t[l];
+        tm[8] = -(dm * (float)sumi);
+    } else {
+        if constexpr (MASKED) half_ints_q6<true>(w, q6m + 256 * half, t);
+        else half_ints_q6<false>(w, rec + 128 * half, t);
+        join_halves(t);
+        const float d = h2f(w.d) * da;
+#pragma unroll
+        for (int l = 0; l < 8; ++l) tm[l] = d * (float)t[l];
+        tm[8] = 0.f;
+    }
+}
+// x86 numerics: the whole unit's x86 terms into the fold buffer as unit_store_x86 writes
+// them (`store`: the even lane of a valid unit)
+template <int T>
+__device__ __forceinline__ void half_store_x86(const HalfW<T>& w, const uint8_t* rec, uint32_t half, float* F, int r,
+                                               int ul, int lr, bool store) {
+    int t[8];
+    float d, dm = 0.f;
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};
+    const float da = *(const float*)(rec + kRecD);
+    if constexpr (T == T_Q4_K) {
+        int pr[2];
+        half_ints_q4(w, rec, half, t, pr);
+        join_halves(t);
+        // the even lane holds prod[0], prod[1]; the odd lane's are prod[2], prod[3]
+        const int q0 = xor_partner_i<1>(pr[0]), q1 = xor_partner_i<1>(pr[1]);
+        ms[0] = (float)pr[0];
+        ms[1] = (float)pr[1];
+        ms[2] = (float)q0;
+        ms[3] = (float)q1;
+        d = da * h2f(w.s.x);
+        dm = -da * h2f(w.s.x >> 16);
+    } else {
+        half_ints_q6_x86(w, rec + 128 * half, t);
+        join_halves(t);
+        d = da * h2f(w.d);
+    }
+    if (store) {
+        float* S = F + (size_t)r * 12 * lr + ul;
+#pragma unroll
+        for (int l = 0; l < 8; ++l) S[l * lr] = (float)t[l];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) S[(8 + k) * lr] = ms[k];
+        float* D = F + kX86KD + (size_t)r * 2 * lr + ul;
+        D[0] = d;
+        D[lr] = dm;
+    }
+}
+
 // get_rows: element e of row `row` dequantized from the device layout (bit-exact with
 // upstream dequantize_row_*)
 __device__ __forceinline__ float dequant_elem(const Seg& w, int row, int e, int cols) {

@@ -12,6 +12,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 
 namespace llmi {
 
@@ -48,16 +49,25 @@ static int g_split_by_pairs = getenv("LLMI_SPLIT_BY_PAIRS") ? atoi(getenv("LLMI_
 #define MV_STAMP(I, V)
 #endif
 
-template <int ACT, bool NORM, int EPI, int T, int NP, int NT = kMVThreads, int X86 = 0>
-__device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds& L, float* F, int t0, int G, int tbeg,
-                                                      int tend) {
+// US = 2: split units (mv_device.h "Split units"): g.lr counts units, the lane pair (2k, 2k + 1)
+// is unit slot k of the task, each lane holds half a unit (HalfW) and the even one stores the
+// terms; every task of the range is of type T (the launcher checks).
+template <int ACT, bool NORM, int EPI, int T, int NP, int NT = kMVThreads, int X86 = 0, int US = 1>
+__device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds& L, float* F, const TaskGeo& g, int t0,
+                                                      int G, int tbeg, int tend) {
+    using W = std::conditional_t<US == 2, HalfW<US == 2 ? T : T_Q4_K>, UnitW<T>>;
     int pos = 0;
     if constexpr (EPI == EPI_QKV) pos = A.st->pos;
     unsigned long long best = 0;
     const int lane = threadIdx.x & 63;
-    const TaskGeo g = task_geo(A);
     const int S = EPI == EPI_SWIGLU ? 2 * g.nj : g.nj;
-    const int r = lane / g.lr, ul = lane - r * g.lr;
+    const int slot = US == 2 ? lane >> 1 : lane;
+    [[maybe_unused]] const uint32_t half = lane & 1;
+    const int r = slot / g.lr, ul = slot - r * g.lr;
+    const auto load = [&](const Seg& s, uint32_t row, uint32_t u) {
+        if constexpr (US == 2) return load_half<T>(s, row, u, g.U, half);
+        else return load_unit<T>(s, row, u, g.U);
+    };
 
     int task = t0;
     MV_STAMP(0, MV_NOW)
@@ -80,7 +90,7 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds
     // idle wave reads unit 0 of row 0, so the prologue's first wait counts only the activation)
     // (prefetch distance 2 -- three rotating register buffers in a 3x unrolled loop --
     // measured slower on every shape: gate+up 16.9 -> 21.2 us, 516 -> 433 tok/s)
-    UnitW<T> cur = load_unit<T>(sg, pipe ? lu.row : 0u, pipe ? lu.u : 0u, g.U);
+    W cur = load(sg, pipe ? lu.row : 0u, pipe ? lu.u : 0u);
     if (img) mv_img_finish<2 * NP + 1, NT>(A, L, RI);
     else mv_prologue_finish<ACT, NORM, NP, NT, X86>(A, L, R);
     __syncthreads();
@@ -101,7 +111,7 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds
         // twice per trip with the two register buffers' roles swapped (ping-pong), so no
         // `cur = nxt` copy of the 36-52 registers of a unit is made per sub-item (Q6_K:
         // ~130 v_mov of the ~885 VALU of a sub-item, and its matvecs are VALU-bound).
-        auto step = [&](UnitW<T>& cur, UnitW<T>& nxt) -> bool {
+        auto step = [&](W& cur, W& nxt) -> bool {
             // next sub-item: (task, s+1) or (task+G, 0); uniform control flow
             int tn = task, sn = s + 1;
             Sub bn = b;
@@ -124,8 +134,21 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds
             // always issue the prefetch (straight-line vmcnt counting); past the wave's last
             // sub-item every lane reads unit 0 of row 0 -- one line per part per wave instead
             // of a nontemporal re-read of the wave's 9-14 KB (FETCH_SIZE: +14 MB per gate+up)
-            nxt = load_unit<T>(sgn, has_next ? lun.row : 0u, has_next ? lun.u : 0u, g.U);
+            nxt = load(sgn, has_next ? lun.row : 0u, has_next ? lun.u : 0u);
             float tm[9];
+            if constexpr (US == 2) {
+                const uint8_t* rec = L.act + (size_t)lu.u * kRec;
+                LaneUnit le = lu;  // the even lane stores the pair's terms
+                le.valid = lu.valid && half == 0;
+                if constexpr (X86) {
+                    half_store_x86<T>(cur, rec, half, F, r, ul, g.lr, le.valid);
+                } else {
+                    const uint8_t* mrec = nullptr;
+                    if constexpr (T == T_Q6_K && kQ6Masked) mrec = q6m + (size_t)lu.u * kQ6MaskRec;
+                    half_terms<T, kQ6Masked>(cur, rec, mrec, half, tm);
+                }
+                sub_finish<ACT, EPI, MVArgs, X86>(A, F, g, s, b, sg, tm, le, r, ul, acc, vg, pos, best);
+            } else {
             if constexpr (X86)
                 unit_store_x86<T>(cur, L.act + (size_t)lu.u * kRec, F, r, ul, g.lr, g.R, lu.valid);
             else if constexpr (T == T_Q6_K && kQ6Masked)
@@ -133,6 +156,7 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds
             else
                 unit_terms<T>(cur, L.act + (size_t)lu.u * kRec, tm);
             sub_finish<ACT, EPI, MVArgs, X86>(A, F, g, s, b, sg, tm, lu, r, ul, acc, vg, pos, best);
+            }
 #if defined(LLMI_EXP_TRACE)
             ++nsub_done;
             if (nsub_done == 1) { MV_STAMP(2, MV_NOW) }
@@ -147,21 +171,22 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds
             return true;
         };
 #if LLMI_MV_PINGPONG
-        UnitW<T> other;
+        W other;
         for (;;) {
             if (!step(cur, other)) break;
             if (!step(other, cur)) break;
         }
 #else
         for (;;) {
-            UnitW<T> nxt;
+            W nxt;
             if (!step(cur, nxt)) break;
             cur = nxt;
         }
 #endif
     }
     // remaining tasks of other types (or all tasks if the first was not of type T)
-    for (; task < tend; task += G) task_any<ACT, EPI, MVArgs, X86>(A, L, F, g, task, r, ul, pos, best);
+    if constexpr (US == 1)
+        for (; task < tend; task += G) task_any<ACT, EPI, MVArgs, X86>(A, L, F, g, task, r, ul, pos, best);
     MV_STAMP(3, MV_NOW)
     MV_STAMP(5, ((unsigned long long)(__builtin_amdgcn_s_getreg(6164) & 15) << 32) | (unsigned)nsub_done)
     return best;
@@ -194,12 +219,12 @@ __global__ __launch_bounds__(NT) void k_matvec(MVArgs A) {
                 tb = A.split_tasks;
             }
         }
-        best = mv_body<ACT, NORM, EPI, T, NP, NT, X86>(A, L, F, t0, G, tb, te);
+        best = mv_body<ACT, NORM, EPI, T, NP, NT, X86>(A, L, F, task_geo(A), t0, G, tb, te);
     } else {
         if ((int)blockIdx.x < A.split_wgs)
-            best = mv_body<ACT, NORM, EPI, T, NP, NT, X86>(A, L, F, blockIdx.x * NW + wave, A.split_wgs * NW, 0, A.split_tasks);
+            best = mv_body<ACT, NORM, EPI, T, NP, NT, X86>(A, L, F, task_geo(A), blockIdx.x * NW + wave, A.split_wgs * NW, 0, A.split_tasks);
         else
-            best = mv_body<ACT, NORM, EPI, T2, NP, NT, X86>(A, L, F, A.split_tasks + (blockIdx.x - A.split_wgs) * NW + wave,
+            best = mv_body<ACT, NORM, EPI, T2, NP, NT, X86>(A, L, F, task_geo(A), A.split_tasks + (blockIdx.x - A.split_wgs) * NW + wave,
                                                             (gridDim.x - A.split_wgs) * NW, A.split_tasks, A.ntasks);
     }
     if constexpr (EPI == EPI_LOGITS) {
@@ -450,6 +475,102 @@ hipError_t mv_dispatch_epi(const MVArgs& a, int epi, dim3 grid, size_t lds, hipS
 template <bool NORM, int T, int T2, int X86>
 hipError_t mv_qkv2_launch(const MVArgs& a, int split_tasks, dim3 grid, size_t lds, hipStream_t s) {
     return mv_launch2<0, NORM, T, T2, EPI_QKV, 1, X86>(a, split_tasks, grid, lds, s);
+}
+
+// ----------------------------------------------------------------------------------
+// Split-unit launches (mv_device.h "Split units"): short single-round launches whose waves
+// each carry one sub-item on one exposed chain run with two lanes per unit -- twice the
+// waves, half the chain.  K-quants only; one prologue sub-block per thread in registers
+// (NP = 1; wider rows load the rest in the prologue's tail loop).  T2 == T: one type, every
+// unit split.  T2 != T: the two type groups of a QKV launch by workgroup as in k_matvec,
+// group 1 (tasks [0, split_tasks) of geometry lr / rpt, US lanes per unit) on workgroups
+// [0, split_wgs), group 2 (tasks [t2beg, t2end) of geometry lr2 / rpt2, US2 lanes per unit)
+// on the rest.  (Group 2 on the low block indices, so that the slower type is dispatched first,
+// measured the same: profiles/mv_split.)
+// ----------------------------------------------------------------------------------
+template <bool NORM, int EPI, int T, int T2, int NT, int X86, int US, int US2>
+__global__ __launch_bounds__(NT) void k_matvec_split(MVArgs A) {
+    constexpr int NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const Lds L = carve(smem, 0, A.cols);
+    const int wave = uniform((int)(threadIdx.x >> 6));
+    float* F = (float*)(smem + fold_off(0, A.cols, NW)) + wave * fold_stride(0, X86, 1, 4);
+    if constexpr (T2 == T) {
+        static_assert(US == 2 && US2 == 2, "single-type split launches split every unit");
+        mv_body<0, NORM, EPI, T, 1, NT, X86, 2>(A, L, F, task_geo_split(A, A.lr, A.rpt), blockIdx.x * NW + wave,
+                                                 gridDim.x * NW, 0, A.ntasks);
+    } else {
+        if ((int)blockIdx.x < A.split_wgs) {
+            const TaskGeo g = US == 2 ? task_geo_split(A, A.lr, A.rpt) : task_geo(A);
+            mv_body<0, NORM, EPI, T, 1, NT, X86, US>(A, L, F, g, blockIdx.x * NW + wave, A.split_wgs * NW, 0, A.split_tasks);
+        } else {
+            const int bi = (int)blockIdx.x - A.split_wgs, nb2 = (int)gridDim.x - A.split_wgs;
+            TaskGeo g = task_geo_split(A, A.lr2, A.rpt2);
+            if constexpr (US2 == 1) {
+                g.lr = A.lr2;
+                g.nj = (g.U + g.lr - 1) / g.lr;
+            }
+            mv_body<0, NORM, EPI, T2, 1, NT, X86, US2>(A, L, F, g, A.t2beg + bi * NW + wave, nb2 * NW, A.t2beg, A.t2end);
+        }
+    }
+}
+
+template <bool NORM, int EPI, int T, int NT, int X86>
+static hipError_t mv_split_launch_nt(const MVArgs& a, hipStream_t s) {
+    constexpr int NW = NT / 64;
+    const size_t lds = mv_lds_total(0, a.cols, NW, T, T, X86);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    auto k = k_matvec_split<NORM, EPI, T, T, NT, X86, 2, 2>;
+    const dim3 g = resident_grid(k, dim3((a.ntasks + NW - 1) / NW), lds, NT);
+    launch_k(k, g, dim3(NT), lds, s, true, true, a);
+    return hipGetLastError();
+}
+template <bool NORM, int T, int X86>
+hipError_t mv_split_launch(const MVArgs& a, int epi, int nt, hipStream_t s) {
+    if (a.us != 2 || (nt != 256 && nt != 512)) return hipErrorInvalidValue;
+    for (int i = 0; i < a.nseg; ++i)
+        if (a.seg[i].type != T) return hipErrorInvalidValue;  // mv_body<US = 2> runs one type
+#define LLMI_SPLIT_NT(E_) (nt == 512 ? mv_split_launch_nt<NORM, E_, T, 512, X86>(a, s) : mv_split_launch_nt<NORM, E_, T, 256, X86>(a, s))
+    if (epi == EPI_STORE) return LLMI_SPLIT_NT(EPI_STORE);
+    if (epi == EPI_ADD) return LLMI_SPLIT_NT(EPI_ADD);
+    if constexpr (NORM)
+        if (epi == EPI_QKV) return LLMI_SPLIT_NT(EPI_QKV);
+#undef LLMI_SPLIT_NT
+    return hipErrorInvalidValue;
+}
+
+// The workgroups of a two-group split launch dealt so that the most tasks any wave runs,
+// weighted by the group's bytes per task, is least (split_groups for NW-wave workgroups)
+static inline int split_groups_nw(int wgs, int nw, int p1, int p2, double b1, double b2) {
+    int best = 1;
+    double best_cost = 1e300;
+    for (int w1 = 1; w1 < wgs; ++w1) {
+        const int n1 = w1 * nw, n2 = (wgs - w1) * nw;
+        const double c = std::max((double)((p1 + n1 - 1) / n1) * b1, (double)((p2 + n2 - 1) / n2) * b2);
+        if (c < best_cost) { best_cost = c; best = w1; }
+    }
+    return best;
+}
+template <int NT, int X86, int US>
+static hipError_t mv_split_qkv2_launch_nt(const MVArgs& a0, hipStream_t s) {
+    constexpr int NW = NT / 64;
+    const size_t lds = mv_lds_total(0, a0.cols, NW, T_Q4_K, T_Q6_K, X86);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    auto k = k_matvec_split<true, EPI_QKV, T_Q4_K, T_Q6_K, NT, X86, US, 2>;
+    MVArgs a = a0;
+    const int p1 = a.split_tasks, p2 = a.t2end - a.t2beg;
+    const dim3 g = resident_grid(k, dim3((p1 + NW - 1) / NW + (p2 + NW - 1) / NW), lds, NT);
+    if (g.x < 2) return hipErrorInvalidValue;
+    // (a wave's time goes with its instructions here, not its bytes: a Q6_K half unit costs
+    // about what a whole Q4_K unit does, a Q4_K half unit half of it)
+    a.split_wgs = split_groups_nw((int)g.x, NW, p1, p2, US == 2 ? 1.0 : 2.0, 2.4);
+    launch_k(k, g, dim3(NT), lds, s, true, true, a);
+    return hipGetLastError();
+}
+template <int X86, int US>
+hipError_t mv_split_qkv2_launch(const MVArgs& a, int nt, hipStream_t s) {
+    if (a.us != US || a.us2 != 2 || a.nseg < 2 || a.cols > 16 * 256 || (nt != 256 && nt != 512)) return hipErrorInvalidValue;
+    return nt == 512 ? mv_split_qkv2_launch_nt<512, X86, US>(a, s) : mv_split_qkv2_launch_nt<256, X86, US>(a, s);
 }
 
 }  // namespace llmi
