@@ -370,6 +370,11 @@ int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
  * long-context.  A forced mode outside its path's limits falls back, and this returns the
  * path that runs.  Host only (no device call); < 0 for bad arguments. */
 int32_t llmi_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t kv_bound, int32_t mode);
+/* The form llmi_attention takes in x86 numerics at the KV bound kv_bound under `mode`: 1, 2,
+ * 4 or 8 = one launch of k_a86_h in that pass class (128 U positions per pass), 0 = the
+ * three launches (scores, softmax, PV: past 2048 positions, or mode 3).  Host only (no
+ * device call); < 0 for bad arguments. */
+int32_t llmi_attn_x86_form(int32_t kv_bound, int32_t mode);
 /* One batched-step attention (the batched step's launch_battention) of nt slots (1..8):
  * slot t is a sequence of n_kv[t] live positions (n_kv: HOST array of nt lengths, each
  * 1..n_ctx) with its own query q [nt][n_head*head_dim], caches kc [nt][n_head_kv][n_ctx]
@@ -400,6 +405,18 @@ double llmi_pf_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, in
  * Returns elapsed device microseconds (>= 0) or < 0 on error. */
 double llmi_pf_attention_fa(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
                             const float* q, const uint16_t* kc, const uint16_t* vc, float* out);
+/* One batched-prefill attention in the x86 association (k_pf_a86, what prefill_enqueue
+ * launches for a LLMI_NUMERICS_X86 model): arguments and layouts as llmi_pf_attention,
+ * pos0 + T <= 32768.  Row t equals llmi_attention over n_kv = pos0 + t + 1 positions in
+ * x86 numerics bit for bit.  Only that kernel runs: a KV length past
+ * llmi_pf_attn_x86_max_kv (the kernel's LDS score rows) or a head shape it has no
+ * instantiation for is an error, never another kernel.  Returns elapsed device
+ * microseconds (>= 0) or < 0 on error. */
+double llmi_pf_attention_x86(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
+                             const float* q, const uint16_t* kc, const uint16_t* vc, float* out);
+/* The longest KV (pos0 + T) k_pf_a86 takes for this head shape; the engine runs the rest of
+ * a longer prompt as decode steps.  Host only (no device call); < 0 for bad arguments. */
+int32_t llmi_pf_attn_x86_max_kv(int32_t n_head, int32_t n_head_kv, int32_t head_dim);
 /* Attention microbenchmark: n_kv positions, one launch per layer over >= 512 MB of
  * distinct KV caches, graph-replayed `reps` times; microseconds per launch (< 0 error).
  * mode: 0 auto, 1 fused, 2 split, 3 two-kernel.  trace_dev != NULL (LLMI_EXP_TRACE

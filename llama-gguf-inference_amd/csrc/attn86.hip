@@ -322,9 +322,15 @@ __global__ __launch_bounds__(kA86Threads) void k_ba86_h(BAttnArgs b, int n_head,
     a86_h_body<D, DS, U>(b.a[blockIdx.y], n_head, gq, kvb, 0);
 }
 
+// the form a86_launch takes: k_a86_h's pass class U (1, 2, 4, 8), or 0: the three launches
+int attn_x86_form(int kv_bound, int mode) {
+    if (mode == 3 || kv_bound > kA86MaxKV) return 0;
+    return kv_bound <= 128 ? 1 : kv_bound <= 256 ? 2 : kv_bound <= 512 ? 4 : 8;
+}
+
 template <int D, int G>
 static hipError_t a86_launch(const AttnArgs& a, int n_head, int hk, int kv_bound, hipStream_t s, int mode) {
-    if (mode != 3 && kv_bound <= kA86MaxKV) {
+    if (const int form = attn_x86_form(kv_bound, mode)) {
 #if defined(LLMI_EXPERIMENTS)
         static const int stop = getenv("LLMI_EXP_A86_STOP") ? atoi(getenv("LLMI_EXP_A86_STOP")) : 0;
 #else
@@ -333,9 +339,9 @@ static hipError_t a86_launch(const AttnArgs& a, int n_head, int hk, int kv_bound
         constexpr int DS = 16;
         const size_t lds = (size_t)kv_bound * 4 + (size_t)DS * (kv_bound + 8) * 2;
         const dim3 grid(n_head * (D / DS));
-        if (kv_bound <= 128) launch_k(k_a86_h<D, DS, 1>, grid, dim3(kA86Threads), lds, s, true, true, a, n_head, G, kv_bound, stop);
-        else if (kv_bound <= 256) launch_k(k_a86_h<D, DS, 2>, grid, dim3(kA86Threads), lds, s, true, true, a, n_head, G, kv_bound, stop);
-        else if (kv_bound <= 512) launch_k(k_a86_h<D, DS, 4>, grid, dim3(kA86Threads), lds, s, true, true, a, n_head, G, kv_bound, stop);
+        if (form == 1) launch_k(k_a86_h<D, DS, 1>, grid, dim3(kA86Threads), lds, s, true, true, a, n_head, G, kv_bound, stop);
+        else if (form == 2) launch_k(k_a86_h<D, DS, 2>, grid, dim3(kA86Threads), lds, s, true, true, a, n_head, G, kv_bound, stop);
+        else if (form == 4) launch_k(k_a86_h<D, DS, 4>, grid, dim3(kA86Threads), lds, s, true, true, a, n_head, G, kv_bound, stop);
         else launch_k(k_a86_h<D, DS, 8>, grid, dim3(kA86Threads), lds, s, true, true, a, n_head, G, kv_bound, stop);
         return hipGetLastError();
     }

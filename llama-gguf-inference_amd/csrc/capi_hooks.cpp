@@ -537,6 +537,12 @@ int32_t llmi_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
     return attn_path(n_head, n_head_kv, kv_bound, head_dim, mode);
 }
 
+// The form launch_attention takes in x86 numerics (host only): k_a86_h's pass class, or 0.
+int32_t llmi_attn_x86_form(int32_t kv_bound, int32_t mode) {
+    if (kv_bound <= 0 || mode < 0 || mode > 7) { set_err("llmi_attn_x86_form: bad arguments"); return -1; }
+    return attn_x86_form(kv_bound, mode);
+}
+
 // One batched-step attention (bstep_enqueue's launch_battention) of nt slots: slot t is one
 // sequence with its own caches, query, output, StepState (pos = n_kv[t] - 1) and scratch,
 // laid out as the batched step lays them out; the KV bound is the batch's (its longest slot).
@@ -661,6 +667,47 @@ double llmi_pf_attention_fa(int32_t n_head, int32_t n_head_kv, int32_t head_dim,
     if (e != hipSuccess) { set_err(std::string("llmi_pf_attention_fa: ") + hip_err(e)); return -3; }
     return (double)ms * 1e3;
     API_CATCH(-5)
+}
+
+// The x86 association's prefill kernel alone (k_pf_a86): PfAttn::num set, so launch_pf_attn
+// goes to launch_pf_attn_x86 and to nothing else; what that refuses (a KV length past
+// pf_attn_x86_max_kv, a head shape without an instantiation) is an error here.
+double llmi_pf_attention_x86(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
+                             const float* q, const uint16_t* kc, const uint16_t* vc, float* out) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || T <= 0 ||
+        pos0 < 0 || n_ctx % 256 || pos0 + T > n_ctx || pos0 + T > kPfAttnMaxKV || !q || !kc || !vc || !out) {
+        set_err("llmi_pf_attention_x86: bad arguments");
+        return -1;
+    }
+    API_TRY
+    PfAttn at;
+    at.q = q; at.out = out; at.ldq = n_head * head_dim; at.kc = kc; at.vc = vc;
+    at.n_ctx = n_ctx; at.pos0 = pos0; at.gqa = n_head / n_head_kv; at.max_kv = pos0 + T;
+    at.scale = 1.0f / sqrtf((float)head_dim);
+    at.num = NUMERICS_X86;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, nullptr);
+    hipError_t e = launch_pf_attn(at, n_head, head_dim, T, nullptr);
+    (void)hipEventRecord(e1, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    float ms = 0.f;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (e != hipSuccess) { set_err(std::string("llmi_pf_attention_x86: ") + hip_err(e)); return -3; }
+    return (double)ms * 1e3;
+    API_CATCH(-5)
+}
+
+// The longest KV k_pf_a86 takes for this head shape (host only: no device call).
+int32_t llmi_pf_attn_x86_max_kv(int32_t n_head, int32_t n_head_kv, int32_t head_dim) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128)) {
+        set_err("llmi_pf_attn_x86_max_kv: bad arguments");
+        return -1;
+    }
+    return pf_attn_x86_max_kv(n_head, n_head_kv, head_dim);
 }
 
 double llmi_bench_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_kv, int32_t mode, int32_t reps,

@@ -302,6 +302,8 @@ hipError_t launch_attention_x86(const AttnArgs& a, int n_head, int n_head_kv, in
                                 int mode = 0);
 hipError_t launch_pf_attn_x86(const PfAttn& a, int n_head, int n_head_kv, int head_dim, int T, hipStream_t s);
 int pf_attn_x86_max_kv(int n_head, int n_head_kv, int head_dim);
+// launch_attention_x86's form at this KV bound and mode: k_a86_h's pass class U, 0 = three launches
+int attn_x86_form(int kv_bound, int mode);
 // flash-attention numerics prefill attention (pfattnfa.hip): T rows at pos0.., the bits of
 // T launch_attention_fa steps; pos0 + T <= kFaMaxKV, gqa <= 32 (hipErrorNotSupported)
 hipError_t launch_pf_attn_fa(const PfAttn& a, int n_head, int head_dim, int T, hipStream_t s);

@@ -117,12 +117,16 @@ SIGNATURES = {
     "llmi_device_hash": (C.c_int32, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "llmi_attention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32]),
     "llmi_attn_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "llmi_attn_x86_form": (C.c_int32, [C.c_int32, C.c_int32]),
     "llmi_battention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _P, _P,
                                     _P, _P]),
     "llmi_pf_attention": (C.c_double, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                        _P, C.c_int32, C.c_int64]),
     "llmi_pf_attention_fa": (C.c_double, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                           _P]),
+    "llmi_pf_attention_x86": (C.c_double, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                           _P]),
+    "llmi_pf_attn_x86_max_kv": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     "llmi_replicate": (C.c_int32, [_P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
     "llmi_rccl_unique_id": (C.c_int32, [C.c_char_p, C.c_int32]),
     "llmi_model_fanout": (C.c_int32, [_P, C.c_char_p, C.c_int32, C.c_int32]),

@@ -1022,7 +1022,7 @@ struct or_model {
     struct { const or_tensor *an, *wq, *wk, *wv, *wo, *fn, *wg, *wu, *wd; } *L;
     /* state */
     uint16_t *kc, *vc;       /* [layer][pos][n_head_kv*head_dim] f16 */
-    float *x, *xb, *q, *k, *v, *att, *hb, *hb2, *tmp, *sc;
+    float *x, *xb, *q, *k, *v, *att, *hb, *hb2, *tmp;
     float *tap_embd, *tap_final;
     /* or_model_localize: the decode matrices' anonymous copies */
     uint8_t** local; int n_local;
@@ -1134,9 +1134,8 @@ or_model* or_model_load(const char* path, int n_ctx) {
     m->x = calloc(E, 4); m->xb = calloc(E, 4); m->q = calloc(E, 4);
     m->k = calloc(kvd, 4); m->v = calloc(kvd, 4); m->att = calloc(E, 4);
     m->hb = calloc(F, 4); m->hb2 = calloc(F, 4); m->tmp = calloc(E > F ? E : F, 4);
-    m->sc = calloc((size_t)m->n_head * m->n_ctx, 4);
     m->tap_embd = calloc(E, 4); m->tap_final = calloc(E, 4);
-    if (!m->kc || !m->vc || !m->sc) OR_FAIL("out of memory");
+    if (!m->kc || !m->vc) OR_FAIL("out of memory");
     return m;
 fail:
     or_model_free(m);
@@ -1218,7 +1217,7 @@ void or_model_free(or_model* m) {
     if (m->fd >= 0) close(m->fd);
     free(m->tensors); free(m->L); free(m->kc); free(m->vc);
     free(m->x); free(m->xb); free(m->q); free(m->k); free(m->v); free(m->att);
-    free(m->hb); free(m->hb2); free(m->tmp); free(m->sc); free(m->tap_embd); free(m->tap_final);
+    free(m->hb); free(m->hb2); free(m->tmp); free(m->tap_embd); free(m->tap_final);
     free(m);
 }
 
@@ -1323,10 +1322,10 @@ static void matvec_multi(const or_tensor* const* T, int n, const float* x, float
  * With OR_X86_F16DOT (the AVX2+F16C build) the dot is the 4 x 8-lane form and vec_mad /
  * the S update are FMA-contracted; without it (the generic scalar build, no FMA) they are
  * a multiply and an add.  Single-query rows only: prompts run through it token by token. */
-static void attn_head_fa(const or_model* m, int l, const float* q, int h, int n_kv, float* out) {
-    const int HK = m->n_head_kv, D = m->head_dim, kvd = HK * D, g = h / (m->n_head / HK);
-    const uint16_t* kl = m->kc + ((size_t)l * m->n_ctx) * kvd;
-    const uint16_t* vl = m->vc + ((size_t)l * m->n_ctx) * kvd;
+/* kb: the KV head's K rows (position t at kb + t * kts, D contiguous f16); vb: its V (position
+ * t, dim d at vb + t * vts + d * vds): the model's caches and or_attention's layouts alike */
+static void attn_head_fa(int D, const float* q, const uint16_t* kb, size_t kts, const uint16_t* vb, size_t vts, size_t vds,
+                         int n_kv, float* out) {
     const float scale = 1.0f / sqrtf((float)D);
     const int x86 = (g_x86 & OR_X86_F16DOT) != 0;
     float qf[512], kf[512], vkq[512];
@@ -1334,8 +1333,8 @@ static void attn_head_fa(const or_model* m, int l, const float* q, int h, int n_
     for (int d = 0; d < D; ++d) { qf[d] = llmi_h2f(llmi_f2h(q[d])); vkq16[d] = 0; }
     float S = 0.0f, M = -INFINITY;
     for (int t = 0; t < n_kv; ++t) {
-        const uint16_t* kr = kl + (size_t)t * kvd + (size_t)g * D;
-        const uint16_t* vr = vl + (size_t)t * kvd + (size_t)g * D;
+        const uint16_t* kr = kb + (size_t)t * kts;
+        const uint16_t* vr = vb + (size_t)t * vts;
         float sc;
         if (x86) {
             for (int d = 0; d < D; ++d) kf[d] = llmi_h2f(kr[d]);
@@ -1357,8 +1356,8 @@ static void attn_head_fa(const or_model* m, int l, const float* q, int h, int n_
             vs = llmi_expf_glibc(sc - M, 1);
         }
         for (int d = 0; d < D; ++d)
-            vkq16[d] = llmi_f2h(x86 ? fmaf(llmi_h2f(vr[d]), vs, llmi_h2f(vkq16[d]))
-                                    : llmi_h2f(vkq16[d]) + llmi_h2f(vr[d]) * vs);
+            vkq16[d] = llmi_f2h(x86 ? fmaf(llmi_h2f(vr[d * vds]), vs, llmi_h2f(vkq16[d]))
+                                    : llmi_h2f(vkq16[d]) + llmi_h2f(vr[d * vds]) * vs);
         S = x86 ? fmaf(S, ms, vs) : S * ms + vs;
     }
     const float S_inv = S == 0.0f ? 0.0f : 1.0f / S;
@@ -1366,15 +1365,18 @@ static void attn_head_fa(const or_model* m, int l, const float* q, int h, int n_
     for (int d = 0; d < D; ++d) out[d] = vkq[d] * S_inv;
 }
 
-/* Non-flash attention of query head h (roped q, f32[D]) over the layer's first n_kv
- * cached positions: kq = mul_mat(K_f16, q) with q rounded to f16 (ggml_vec_dot_f16,
- * double sum), soft_max_ext(kq, scale 1/sqrt(D)) with a double sum, kqv =
- * mul_mat(V_f16, kq) with the probabilities rounded to f16.  w: f32[n_kv] scratch. */
-static void attn_head(const or_model* m, int l, const float* q, int h, int n_kv, float* w, float* out) {
-    if (g_x86 & OR_X86_FA) { attn_head_fa(m, l, q, h, n_kv, out); return; }
-    const int HK = m->n_head_kv, D = m->head_dim, kvd = HK * D, g = h / (m->n_head / HK);
-    const uint16_t* kl = m->kc + ((size_t)l * m->n_ctx) * kvd;
-    const uint16_t* vl = m->vc + ((size_t)l * m->n_ctx) * kvd;
+/* Non-flash attention of one query head (roped q, f32[D]) over the first n_kv positions of
+ * its KV head (kb / vb with strides as attn_head_fa): kq = mul_mat(K_f16, q) with q rounded
+ * to f16 (ggml_vec_dot_f16, double sum), soft_max_ext(kq, scale 1/sqrt(D)) with a double
+ * sum, kqv = mul_mat(V_f16, kq) with the probabilities rounded to f16.  w: f32 scratch,
+ * n_kv floats, in the x86 f16-dot association 3 * ((n_kv + 31) & ~31) (the padded p and V
+ * rows of the PV dot behind the scores: attn_scratch_floats). */
+static size_t attn_scratch_floats(int n_kv) {
+    return (g_x86 & OR_X86_F16DOT) && !(g_x86 & OR_X86_FA) ? 3 * (((size_t)n_kv + 31) & ~(size_t)31) : (size_t)n_kv;
+}
+static void attn_head(int D, const float* q, const uint16_t* kb, size_t kts, const uint16_t* vb, size_t vts, size_t vds,
+                      int n_kv, float* w, float* out) {
+    if (g_x86 & OR_X86_FA) { attn_head_fa(D, q, kb, kts, vb, vts, vds, n_kv, out); return; }
     const float kq_scale = 1.0f / sqrtf((float)D);
     /* f16-rounded q and K/V values as floats (the same values vd_f16 and the PV loop
      * form per element; converted once instead of once per use) */
@@ -1383,7 +1385,7 @@ static void attn_head(const or_model* m, int l, const float* q, int h, int n_kv,
     float mx = -INFINITY;
     const int f16x = (g_x86 & OR_X86_F16DOT) != 0;
     for (int t = 0; t < n_kv; ++t) {
-        const uint16_t* kr = kl + (size_t)t * kvd + (size_t)g * D;
+        const uint16_t* kr = kb + (size_t)t * kts;
         if (f16x) {
             float kf[512];
             for (int d = 0; d < D; ++d) kf[d] = llmi_h2f(kr[d]);
@@ -1415,12 +1417,12 @@ static void attn_head(const or_model* m, int l, const float* q, int h, int n_kv,
     for (int t = 0; t < n_kv; ++t) w[t] = llmi_h2f(llmi_f2h(w[t] * inv));  /* p rounded to f16 */
     if (f16x) {  /* mul_mat(V^T, p): one f16 dot over the positions (padded to 32 with p = 0) per dim */
         const int np = (n_kv + 31) & ~31;
-        float vf[8192], pf[8192];
-        if (np > 8192) return;
+        float* pf = w + np;
+        float* vf = pf + np;
         for (int t = n_kv; t < np; ++t) pf[t] = 0.f;
         for (int t = 0; t < n_kv; ++t) pf[t] = w[t];
         for (int d = 0; d < D; ++d) {
-            for (int t = 0; t < n_kv; ++t) vf[t] = llmi_h2f(vl[(size_t)t * kvd + (size_t)g * D + d]);
+            for (int t = 0; t < n_kv; ++t) vf[t] = llmi_h2f(vb[(size_t)t * vts + (size_t)d * vds]);
             for (int t = n_kv; t < np; ++t) vf[t] = 0.f;
             out[d] = x86_dot_f16f(np, vf, pf);
         }
@@ -1429,10 +1431,59 @@ static void attn_head(const or_model* m, int l, const float* q, int h, int n_kv,
     double acc[512];
     for (int d = 0; d < D; ++d) acc[d] = 0.0;
     for (int t = 0; t < n_kv; ++t) {  /* per d the same sequential double sum over t */
-        const uint16_t* vr = vl + (size_t)t * kvd + (size_t)g * D;
-        for (int d = 0; d < D; ++d) acc[d] += (double)(llmi_h2f(vr[d]) * w[t]);
+        const uint16_t* vr = vb + (size_t)t * vts;
+        for (int d = 0; d < D; ++d) acc[d] += (double)(llmi_h2f(vr[d * vds]) * w[t]);
     }
     for (int d = 0; d < D; ++d) out[d] = (float)acc[d];
+}
+
+/* The H heads of T queries (row t at q + t * ldq, over n_kv0 + t positions, to out + t *
+ * ldq), each thread with heap scratch sized from the longest row (no fixed arrays: any
+ * context length).  Nonzero, g_err set and out untouched if a thread's scratch cannot be
+ * allocated. */
+static int attn_heads(int H, int HK, int D, int T, size_t ldq, const float* q, const uint16_t* K, size_t khs, size_t kts,
+                      const uint16_t* V, size_t vhs, size_t vts, size_t vds, int n_kv0, float* out, int nth) {
+    const size_t nw = attn_scratch_floats(n_kv0 + T - 1);
+    int fail = 0;
+#pragma omp parallel num_threads(nth > 0 ? nth : 1)
+    {
+        float* w = malloc(nw * sizeof(float));
+        if (!w) {
+#pragma omp atomic write
+            fail = 1;
+        }
+#pragma omp barrier
+        int stop;
+#pragma omp atomic read
+        stop = fail;
+        if (!stop) {
+#pragma omp for schedule(dynamic, 1)
+            for (int th = 0; th < T * H; ++th) {
+                const int t = th / H, h = th % H, g = h / (H / HK);
+                attn_head(D, q + (size_t)t * ldq + (size_t)h * D, K + (size_t)g * khs, kts, V + (size_t)g * vhs, vts, vds,
+                          n_kv0 + t, w, out + (size_t)t * ldq + (size_t)h * D);
+            }
+        }
+        free(w);
+    }
+    if (fail) snprintf(g_err, sizeof g_err, "attention: out of memory for %zu scratch floats per thread", nw);
+    return fail;
+}
+
+/* Attention at kernel level, in the layouts of the GPU hooks (llmi_attention): q [H][D]
+ * f32 (roped), K [HK][n_ctx][D] and V [HK][D][n_ctx] f16, out [H][D], over the first n_kv
+ * positions, in the numerics of the current mode flags (generic, the x86 association,
+ * either with OR_X86_FA): the bodies or_decode and or_prefill run.  0, or nonzero with
+ * or_last_error set and out untouched. */
+int or_attention(int n_head, int n_head_kv, int head_dim, int n_kv, int n_ctx, const float* q, const uint16_t* K,
+                 const uint16_t* V, float* out, int nthreads) {
+    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || head_dim <= 0 || head_dim > 512 || head_dim % 32 ||
+        n_kv <= 0 || n_kv > n_ctx || !q || !K || !V || !out) {
+        snprintf(g_err, sizeof g_err, "or_attention: bad arguments");
+        return 1;
+    }
+    return attn_heads(n_head, n_head_kv, head_dim, 1, 0, q, K, (size_t)n_ctx * head_dim, (size_t)head_dim, V,
+                      (size_t)head_dim * n_ctx, 1, (size_t)n_ctx, n_kv, out, nthreads);
 }
 
 /* One decode step of llm_build_llama [upstream llama-model.cpp] with the non-flash
@@ -1463,8 +1514,7 @@ int or_decode(or_model* m, int32_t token, int32_t pos, float* logits, int nth) {
         uint16_t* kl = m->kc + ((size_t)l * m->n_ctx) * kvd;
         uint16_t* vl = m->vc + ((size_t)l * m->n_ctx) * kvd;
         for (int i = 0; i < kvd; ++i) { kl[(size_t)pos * kvd + i] = llmi_f2h(m->k[i]); vl[(size_t)pos * kvd + i] = llmi_f2h(m->v[i]); }
-#pragma omp parallel for schedule(static) num_threads(nth > 0 ? nth : 1)
-        for (int h = 0; h < H; ++h) attn_head(m, l, m->q + (size_t)h * D, h, n_kv, m->sc + (size_t)h * m->n_ctx, m->att + (size_t)h * D);
+        if (attn_heads(H, HK, D, 1, 0, m->q, kl, (size_t)D, (size_t)kvd, vl, (size_t)D, (size_t)kvd, 1, n_kv, m->att, nth)) return 2;
         matvec_t(m->L[l].wo, m->att, m->tmp, nth);
         for (int i = 0; i < E; ++i) m->x[i] = m->tmp[i] + m->x[i];
         or_rms_norm_mul(m->x, (const float*)m->L[l].fn->data, m->xb, E, m->eps);
@@ -1529,6 +1579,7 @@ int or_prefill(or_model* m, const int32_t* tokens, int T, int pos0, int nth) {
         if (tokens[t] < 0 || tokens[t] >= m->n_vocab) { snprintf(g_err, sizeof g_err, "token %d out of range", tokens[t]); return -1; }
     const int E = m->n_embd, H = m->n_head, HK = m->n_head_kv, D = m->head_dim, F = m->n_ff, kvd = HK * D, QD = H * D;
     const float* ff = m->rope_freqs ? (const float*)m->rope_freqs->data : NULL;
+    int rc = 0;
     float* X = malloc((size_t)T * E * 4); float* XB = malloc((size_t)T * E * 4); float* TMP = malloc((size_t)T * E * 4);
     float* Q = malloc((size_t)T * QD * 4); float* K = malloc((size_t)T * kvd * 4); float* V = malloc((size_t)T * kvd * 4);
     float* ATT = malloc((size_t)T * QD * 4); float* HB = malloc((size_t)T * F * 4); float* HB2 = malloc((size_t)T * F * 4);
@@ -1549,15 +1600,9 @@ int or_prefill(or_model* m, const int32_t* tokens, int T, int pos0, int nth) {
                 vl[(size_t)(pos0 + t) * kvd + i] = llmi_f2h(V[(size_t)t * kvd + i]);
             }
         }
-#pragma omp parallel num_threads(nth > 0 ? nth : 1)
-        {
-            float* w = malloc((size_t)m->n_ctx * 4);
-#pragma omp for schedule(dynamic, 1)
-            for (int th = 0; th < T * H; ++th) {
-                const int t = th / H, h = th % H;
-                attn_head(m, l, Q + (size_t)t * QD + (size_t)h * D, h, pos0 + t + 1, w, ATT + (size_t)t * QD + (size_t)h * D);
-            }
-            free(w);
+        if (attn_heads(H, HK, D, T, (size_t)QD, Q, kl, (size_t)D, (size_t)kvd, vl, (size_t)D, (size_t)kvd, 1, pos0 + 1, ATT, nth)) {
+            rc = 2;  /* the caches hold this prompt's rows up to layer l: the caller starts over */
+            break;
         }
         matmul_t(m->L[l].wo, ATT, T, TMP, nth);
         for (size_t i = 0; i < (size_t)T * E; ++i) X[i] = TMP[i] + X[i];
@@ -1575,10 +1620,12 @@ int or_prefill(or_model* m, const int32_t* tokens, int T, int pos0, int nth) {
             memcpy(m->hb, HB + (size_t)(T - 1) * F, (size_t)F * 4);
         }
     }
-    memcpy(m->x, X + (size_t)(T - 1) * E, (size_t)E * 4);
-    memcpy(m->tap_final, m->x, (size_t)E * 4);
+    if (!rc) {
+        memcpy(m->x, X + (size_t)(T - 1) * E, (size_t)E * 4);
+        memcpy(m->tap_final, m->x, (size_t)E * 4);
+    }
     free(X); free(XB); free(TMP); free(Q); free(K); free(V); free(ATT); free(HB); free(HB2);
-    return 0;
+    return rc;
 }
 
 int or_tap(const or_model* m, int which, float* out) {

@@ -88,6 +88,14 @@ void or_model_info(const or_model* m, int64_t* out);
 /* Processes one token at position pos (KV cache holds 0..pos-1); writes f32[n_vocab] logits. */
 int or_decode(or_model* m, int32_t token, int32_t pos, float* logits, int nthreads);
 void or_kv_clear(or_model* m);
+/* Attention alone, in the layouts of the GPU's kernel-level hooks: q f32 [n_head][head_dim]
+ * (roped), K f16 [n_head_kv][n_ctx][head_dim], V f16 [n_head_kv][head_dim][n_ctx], out f32
+ * [n_head][head_dim], over the first n_kv positions, in the numerics of the current mode
+ * flags (or_set_x86_mode: generic, the x86 association, either with the flash-attention
+ * bit) -- the bodies or_decode and or_prefill run.  0, or nonzero with or_last_error set
+ * and out untouched. */
+int or_attention(int n_head, int n_head_kv, int head_dim, int n_kv, int n_ctx, const float* q, const uint16_t* K,
+                 const uint16_t* V, float* out, int nthreads);
 /* Debug taps of the last or_decode: which = 0 embedding row, 1 final hidden (pre-norm) */
 int or_tap(const or_model* m, int which, float* out);
 /* Algorithmic bytes streamed per decoded token (weights + one embd row + KV at ctx). */

@@ -94,6 +94,7 @@ def lib() -> C.CDLL:
         "or_set_x86_mode": (C.c_int, [C.c_int]),
         "or_quantize_act": (C.c_int, [C.c_int, P, P, C.c_int64]),
         "or_get_x86_mode": (C.c_int, []),
+        "or_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, C.c_int]),
     }
     for k, (r, a) in sig.items():
         f = getattr(L, k)
@@ -200,6 +201,24 @@ def matvec(type_: int, W: np.ndarray, rows: int, cols: int, x: np.ndarray, threa
     with x86_mode(x86):
         assert lib().or_matvec(type_, _p(W), rows, cols, _p(x), _p(y), threads or nthreads()) == 0
     return y
+
+
+def attention(q: np.ndarray, K: np.ndarray, V: np.ndarray, n_kv: int, x86: int | None = None,
+              threads: int = 0) -> np.ndarray:
+    """or_attention: q f32 [H][D], K f16 [HK][n_ctx][D], V f16 [HK][D][n_ctx] (the GPU hooks'
+    layouts) over the first n_kv positions -> f32 [H][D]; x86: the association flags for the
+    call (0 generic, X86_ALL, either | X86_FA; None: the current mode)."""
+    H, D = q.shape
+    HK, n_ctx, _ = K.shape
+    assert K.dtype == np.float16 and V.dtype == np.float16 and K.shape == (HK, n_ctx, D) and V.shape == (HK, D, n_ctx)
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    K, V = np.ascontiguousarray(K), np.ascontiguousarray(V)
+    out = np.full((H, D), np.nan, dtype=np.float32)
+    with x86_mode(x86):
+        rc = lib().or_attention(H, HK, D, int(n_kv), n_ctx, _p(q), _p(K), _p(V), _p(out), threads or nthreads())
+    if rc != 0:
+        raise RuntimeError(f"or_attention rc={rc}: " + lib().or_last_error().decode())
+    return out
 
 
 def expf(x: float) -> float:
