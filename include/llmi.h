@@ -230,7 +230,8 @@ int32_t llmi_profile_kernels(struct llama_context* ctx, llama_token first, int32
  *   "xtag_skew"       1: k_attn_x consumers wait for a tag no producer writes (with
  *                     xspin_limit 0: every such wait gives up at once; fault-path test)
  *   "numerics"        this thread's numerics for the kernel-level entry points below
- *                     (llmi_repack's byte order, llmi_matvec, llmi_bmv, llmi_quantize_act,
+ *                     (llmi_repack's byte order, llmi_matvec, llmi_bmv, llmi_mv_epilogue,
+ *                     llmi_quantize_act,
  *                     llmi_attention, llmi_battention, llmi_pf_attention,
  *                     llmi_pf_attention_fa):
  *                     LLMI_NUMERICS_* */
@@ -341,6 +342,74 @@ int32_t llmi_pf_gemm(int32_t type, const void* w_dev, int64_t rows, int64_t cols
  * any device call.  0 on success. */
 int32_t llmi_bmv(int32_t type, const void* w_dev, int64_t rows, int64_t cols, const float* x_dev,
                  const float* norm_w_dev, float eps, int32_t nt, float* y_dev, int32_t kernel);
+/* One QKV, SwiGLU or logits launch of a step at kernel level (no model): the fused RMSNorm,
+ * the quantized matvec, and the epilogue that does arithmetic and scattered writes of its
+ * own -- RoPE with the f16 K write and the transposed f16 V write; silu(gate) * up; the
+ * logits store with the device argmax key.
+ *
+ * kernel  0  launch_matvec (k_matvec; honours the "mv_unit_split" / "mv_split_nt" test
+ *            options, so k_matvec_split is reachable); one token
+ *         1  launch_mvn (k_mvn), 1..8 tokens
+ *         2  launch_pf_quant + launch_bmm (k_bmd, or k_bmm under LLMI_BMM_DMA=0), 1..8 tokens
+ *         3  launch_pf_quant + launch_pf_gemm (k_pf_gemm), any nt > 0; no LOGITS
+ *         4  launch_pf_quant + launch_bmm_qkv2 (k_bmd2), 1..8 tokens; a QKV of two type
+ *            groups only
+ * epi     LLMI_EPI_QKV      w[0..2] = q, k, v (rows[1] == rows[2], each a multiple of
+ *                           head_dim).  The three segments are grouped into launches as
+ *                           the engine groups them: kernel 0 by activation kind (the decode
+ *                           step), kernels 1 / 2 by weight type (the batched step), kernel 3
+ *                           as the batched prefill (same-type parts merged under the
+ *                           "pf_qkv_merge" test option while the part before is a multiple
+ *                           of 64 rows).  rope_dev [n_ctx][n_rot/2][cos,sin] is the
+ *                           caller's.  pos (host): kernels 0 / 1 / 2 / 4 one position per
+ *                           token, kernel 3 pos[0] = the first token's position, the others
+ *                           following it.  Outputs: q_dev [nt][rows[0]]; kc_dev [S][HK]
+ *                           [n_ctx][head_dim] and vc_dev [S][HK][head_dim][n_ctx] f16, S =
+ *                           nt caches (one per token slot) for kernels 1 / 2 / 4, S = 1
+ *                           for kernels 0 and 3.  Only the written entries change.
+ *         LLMI_EPI_SWIGLU   w[0..1] = gate, up (equal rows); y_dev [nt][rows[0]].  Kernel 3
+ *                           runs it as the prefill does: a STORE of gate, then
+ *                           EPI_SWIGLU_UP with up.
+ *         LLMI_EPI_LOGITS   w[0]; y_dev [nt][rows[0]]; one StepState of the hook's own per
+ *                           token, at position pos[t] with its key slots zeroed (as k_embed /
+ *                           k_bembed leave them); token_out[t] (host) = the token of the
+ *                           key slots of parity pos[t] & 1, pos_next_out[t] (host) = the
+ *                           state's pos_next.
+ * norm_w_dev is required (the engine always fuses the RMSNorm into these launches).  k_mvn
+ * pads nt to 1, 2, 4 or 8 tokens: x, q and y go through 8-row buffers of the hook's own
+ * (padded rows zero), and the padded slots point at a dummy cache and a dummy state of the
+ * hook's own, as the engine points them at its dummy sequence.  Never a fall-back from the
+ * requested kernel to another: a kernel asked for on arguments it does not take returns
+ * < 0 with llmi_last_error set.  The numerics are this thread's "numerics" test option.
+ * Bad arguments (a null pointer, an unknown type, cols no positive multiple of 256, nt out
+ * of range, n_rot odd or > head_dim, rows no multiple of head_dim, a position outside
+ * 0..n_ctx-1, kernel 3: pos[0] + nt > n_ctx) are rejected before any device call.
+ * 0 on success. */
+enum { LLMI_EPI_QKV = 2, LLMI_EPI_SWIGLU = 3, LLMI_EPI_LOGITS = 4 };
+struct llmi_epilogue_args {
+    int32_t kernel, epi;
+    int32_t type[3];
+    const void* w_dev[3];       /* device layout (llmi_repack) */
+    int64_t rows[3];
+    int64_t cols;
+    const float* x_dev;         /* [nt][cols] */
+    const float* norm_w_dev;    /* [cols] */
+    float eps;
+    int32_t nt;
+    const int32_t* pos;         /* host; QKV and LOGITS */
+    /* QKV */
+    int32_t head_dim, n_rot, n_ctx;
+    const float* rope_dev;
+    float* q_dev;
+    uint16_t* kc_dev;
+    uint16_t* vc_dev;
+    /* SWIGLU, LOGITS */
+    float* y_dev;
+    /* LOGITS (host) */
+    int32_t* token_out;
+    int32_t* pos_next_out;
+};
+int32_t llmi_mv_epilogue(const struct llmi_epilogue_args* args);
 /* the activation quantization the matvec prologue performs, written out in ggml block
  * form (block_q8_K for K-quant weight types, block_q8_0 for Q8_0) for bit-exact checks */
 int32_t llmi_quantize_act(int32_t type, int64_t cols, const float* x_dev, const float* norm_w_dev,

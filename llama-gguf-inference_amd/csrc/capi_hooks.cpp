@@ -361,6 +361,290 @@ int32_t llmi_bmv(int32_t type, const void* w, int64_t rows, int64_t cols, const 
     API_CATCH(-5)
 }
 
+}  // extern "C"
+
+namespace {
+// the device allocations of one hook call, freed on every way out; after a failure every
+// further request returns null and `err` keeps the first error
+struct DevPool {
+    std::vector<void*> all;
+    hipError_t err = hipSuccess;
+    template <class T>
+    T* get(size_t bytes, bool zero = true) {
+        void* p = nullptr;
+        if (err == hipSuccess) err = hipMalloc(&p, bytes ? bytes : 1);
+        if (err != hipSuccess) return nullptr;
+        all.push_back(p);
+        if (zero) err = hipMemset(p, 0, bytes);
+        return (T*)p;
+    }
+    ~DevPool() {
+        for (void* p : all) (void)hipFree(p);
+    }
+};
+// launch_pf_quant's outputs for tpad token rows (llmi_pf_gemm's sizes), zeroed: the padded
+// rows are read
+struct QuantScratch {
+    void* aq = nullptr;
+    int16_t* abs = nullptr;
+    float* ad = nullptr;
+    void* abf = nullptr;
+    QuantScratch(DevPool& P, size_t tpad, size_t cols) {
+        aq = P.get<void>(tpad * cols * 2);
+        abf = P.get<void>(tpad * (cols / 256) * 64);
+        abs = P.get<int16_t>(tpad * (cols / 16) * 2);
+        ad = P.get<float>(tpad * (cols / 32) * 4);
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int32_t llmi_mv_epilogue(const struct llmi_epilogue_args* A) {
+    auto bad = [](const char* what) {
+        set_err(std::string("llmi_mv_epilogue: ") + what);
+        return -1;
+    };
+    if (!A) return bad("null arguments");
+    const int kernel = A->kernel, epi = A->epi, nt = A->nt;
+    if (kernel < 0 || kernel > 4) return bad("kernel outside 0..4");
+    if (epi != EPI_QKV && epi != EPI_SWIGLU && epi != EPI_LOGITS) return bad("epi is none of QKV, SWIGLU, LOGITS");
+    if (kernel == 3 && epi == EPI_LOGITS) return bad("the prefill GEMM has no LOGITS epilogue");
+    if (kernel == 4 && epi != EPI_QKV) return bad("kernel 4 (launch_bmm_qkv2) takes QKV only");
+    const int nw = epi == EPI_QKV ? 3 : epi == EPI_SWIGLU ? 2 : 1;
+    for (int i = 0; i < nw; ++i) {
+        const int t = A->type[i];
+        if (!(t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0)) return bad("unknown weight type");
+        if (!A->w_dev[i]) return bad("null weight");
+        if (A->rows[i] <= 0 || A->rows[i] > INT32_MAX) return bad("rows out of range");
+    }
+    if (A->cols <= 0 || A->cols > INT32_MAX || A->cols % 256) return bad("cols must be a positive multiple of 256");
+    if (!A->x_dev || !A->norm_w_dev) return bad("null x / norm weight (the RMSNorm is always fused)");
+    if (kernel == 0 ? nt != 1 : kernel == 3 ? (nt < 1 || nt > (1 << 20)) : (nt < 1 || nt > kMaxBatch))
+        return bad("nt out of range (kernel 0: 1, kernels 1 / 2 / 4: 1..8, kernel 3: > 0)");
+    const int cols = (int)A->cols, D = A->head_dim, n_ctx = A->n_ctx;
+    const int r0 = (int)A->rows[0];
+    if (epi == EPI_QKV) {
+        if (D <= 0 || D % 2 || n_ctx <= 0) return bad("head_dim must be positive and even, n_ctx positive");
+        if (A->n_rot < 0 || A->n_rot % 2 || A->n_rot > D) return bad("n_rot must be even and at most head_dim");
+        for (int i = 0; i < 3; ++i)
+            if (A->rows[i] % D) return bad("rows must be multiples of head_dim");
+        if (A->rows[1] != A->rows[2]) return bad("k and v must have the same rows");
+        if (!A->rope_dev || !A->pos || !A->q_dev || !A->kc_dev || !A->vc_dev) return bad("null rope / pos / q / kc / vc");
+        if (kernel == 3) {
+            if (A->pos[0] < 0 || (int64_t)A->pos[0] + nt > n_ctx) return bad("pos0 + T > n_ctx");
+        } else {
+            for (int t = 0; t < nt; ++t)
+                if (A->pos[t] < 0 || A->pos[t] >= n_ctx) return bad("position outside 0..n_ctx-1");
+        }
+    } else {
+        if (!A->y_dev) return bad("null y");
+        if (epi == EPI_SWIGLU && A->rows[0] != A->rows[1]) return bad("gate and up must have the same rows");
+        if (epi == EPI_LOGITS) {
+            if (!A->pos || !A->token_out || !A->pos_next_out) return bad("null pos / token_out / pos_next_out");
+            for (int t = 0; t < nt; ++t)
+                if (A->pos[t] < 0 || A->pos[t] == INT32_MAX) return bad("position out of range");
+        }
+    }
+    API_TRY
+    const int num = t_hook_numerics & NUMERICS_X86;
+    Seg seg[3];
+    for (int i = 0, row0 = 0; i < nw; ++i) {
+        seg[i] = seg_at(A->type[i], A->w_dev[i], A->rows[i], cols);
+        seg[i].row0 = epi == EPI_QKV ? row0 : 0;
+        row0 += (int)A->rows[i];
+    }
+    const int nq = r0, nk = epi == EPI_QKV ? (int)A->rows[1] : 0;
+    const int ldy = r0;  // floats per row of the f32 output (q, h or the logits)
+    // the launches' descriptors (kernels 0 / 1 / 2 / 4), grouped as the engine groups them
+    MVArgs base;
+    base.cols = cols; base.nw = A->norm_w_dev; base.eps = A->eps; base.num = num;
+    if (epi == EPI_QKV) {
+        base.rope = A->rope_dev; base.head_dim = D; base.n_rot = A->n_rot; base.n_ctx = n_ctx; base.nq = nq; base.nk = nk;
+    }
+    MVArgs grp[3];
+    int ng = 1, first[3] = {0, 0, 0};
+    if (epi == EPI_QKV) {
+        const Seg qkv[3] = {seg[0], seg[1], seg[2]};
+        ng = qkv_launch_groups(qkv, kernel == 0, base, grp, first);
+    } else {
+        grp[0] = base;
+        grp[0].nseg = nw;
+        for (int i = 0; i < nw; ++i) grp[0].seg[i] = seg[i];
+        grp[0].npairs = epi == EPI_SWIGLU ? r0 : (r0 + 1) / 2;
+    }
+    // never another kernel than the one asked for: what it does not take is refused here,
+    // on the host, before any device call
+    auto one_type = [](const MVArgs& a) {
+        for (int i = 1; i < a.nseg; ++i)
+            if (a.seg[i].type != a.seg[0].type) return false;
+        return true;
+    };
+    if (kernel == 0 || kernel == 1) {
+        for (int g = 0; g < ng; ++g) {
+            MVArgs probe = grp[g];
+            for (int i = 1; i < probe.nseg; ++i)
+                if (act_kind(probe.seg[i].type) != act_kind(probe.seg[0].type))
+                    return bad("launch_matvec / launch_mvn take segments of one activation kind");
+            if (kernel == 1 && !one_type(probe)) return bad("launch_mvn takes segments of one type");
+            if (!mv_geometry(probe, epi)) return bad("the segments cannot be cut into row tasks");
+        }
+    } else if (kernel == 2 || kernel == 4) {
+        if (kernel == 4 && ng != 2) return bad("kernel 4 (launch_bmm_qkv2) takes a QKV of two type groups");
+        for (int g = 0; g < ng; ++g)
+            if (!bmm_ok(grp[g], epi))
+                return bad("the matrix-core kernels do not take these arguments (type, rows % 16, numerics, LLMI_BMM*)");
+    } else {
+        for (int i = 0; i < nw; ++i)
+            if (!pf_gemm_ok(A->type[i], (int)A->rows[i], cols)) return bad("launch_pf_gemm does not take this type / shape");
+        if (epi == EPI_SWIGLU && act_kind(A->type[0]) != act_kind(A->type[1]))
+            return bad("prefill: ffn_gate / ffn_up of different activation kinds");
+    }
+
+    DevPool P;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    hipDeviceProp_t prop;
+    (void)hipGetDeviceProperties(&prop, dev);
+    const int mb = std::max(64, prop.multiProcessorCount * wg_per_cu());
+    const size_t kvl = epi == EPI_QKV ? (size_t)(nk / D) * n_ctx * D : 0;  // elements of one cache
+    // one StepState per token slot + the dummy one of the padded slots
+    const int nslot = kernel == 0 || kernel == 3 ? 1 : nt;
+    std::vector<StepState> hs((size_t)nslot + 1);
+    for (int t = 0; t < nslot; ++t) {
+        StepState& s = hs[(size_t)t];
+        memset(&s, 0, sizeof(s));
+        s.pos = s.pos_next = A->pos && kernel != 3 ? A->pos[t] : 0;
+        s.seq = 1;
+    }
+    memset(&hs[(size_t)nslot], 0, sizeof(StepState));
+    StepState* st = P.get<StepState>(hs.size() * sizeof(StepState));
+    hipError_t e = P.err;
+    if (e == hipSuccess) e = hipMemcpy(st, hs.data(), hs.size() * sizeof(StepState), hipMemcpyHostToDevice);
+    const char* refused = nullptr;
+    if (kernel == 0) {
+        for (int g = 0; g < ng && e == hipSuccess; ++g) {
+            MVArgs& a = grp[g];
+            a.x = A->x_dev; a.st = st;
+            if (epi == EPI_QKV) { a.y = A->q_dev; a.kc = A->kc_dev; a.vc = A->vc_dev; }
+            else a.y = A->y_dev;
+            if (epi == EPI_LOGITS) a.argmax = &st->key[0][0];
+            e = launch_matvec(a, epi, mb, nullptr);
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    } else if (kernel == 3) {
+        const int T = nt, x86 = num ? 1 : 0;
+        const size_t tpad = (size_t)(T + 63) / 64 * 64;
+        QuantScratch q(P, tpad, (size_t)cols);
+        e = P.err;
+        PfGemm g;
+        g.T = T; g.cols = cols; g.aq = q.aq; g.abs = q.abs; g.ad = q.ad; g.abf = q.abf;
+        if (epi == EPI_QKV) {
+            // prefill_enqueue's q / k / v loop, restated (there it is interleaved with the
+            // model's tensors): one quantization per activation kind, consecutive same-type
+            // parts (rows multiples of 64) in one launch
+            g.kc = A->kc_dev; g.vc = A->vc_dev; g.rope = A->rope_dev;
+            g.pos0 = A->pos[0]; g.head_dim = D; g.n_rot = A->n_rot; g.n_ctx = n_ctx;
+            g.y = A->q_dev; g.ldy = nq;
+            int quant_kind = -1;
+            for (int part = 0; part < 3 && e == hipSuccess;) {
+                if (act_kind(A->type[part]) != quant_kind) {
+                    quant_kind = act_kind(A->type[part]);
+                    e = launch_pf_quant(A->x_dev, cols, A->norm_w_dev, A->eps, cols, quant_kind, T, q.aq, q.abs, q.ad, q.abf,
+                                        nullptr, x86);
+                    if (e != hipSuccess) break;
+                }
+                int end = part + 1;
+                while (g_pf_qkv_merge && end < 3 && A->type[end] == A->type[part] && A->rows[end - 1] % 64 == 0) ++end;
+                g.w = seg[part]; g.w.row0 = 0; g.rows = (int)A->rows[part]; g.part = part; g.r1 = g.r2 = 0;
+                if (end > part + 1) {
+                    g.wk = seg[part + 1]; g.wk.row0 = 0;
+                    g.r1 = (int)A->rows[part];
+                    g.r2 = g.r1 + (int)A->rows[part + 1];
+                    g.rows = g.r2;
+                    if (end > part + 2) {
+                        g.wv = seg[part + 2]; g.wv.row0 = 0;
+                        g.rows += (int)A->rows[part + 2];
+                    }
+                }
+                e = launch_pf_gemm(g, EPI_QKV, nullptr);
+                part = end;
+            }
+        } else {  // gate into y, then y = silu(y) * up
+            if (e == hipSuccess)
+                e = launch_pf_quant(A->x_dev, cols, A->norm_w_dev, A->eps, cols, act_kind(A->type[0]), T, q.aq, q.abs, q.ad,
+                                    q.abf, nullptr, x86);
+            g.w = seg[0]; g.w2 = seg[1]; g.rows = r0; g.y = A->y_dev; g.ldy = ldy;
+            if (e == hipSuccess) e = launch_pf_gemm(g, EPI_STORE, nullptr);
+            g.w = seg[1];
+            if (e == hipSuccess) e = launch_pf_gemm(g, EPI_SWIGLU_UP, nullptr);
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    } else {
+        // the batched step's buffers: kMaxBatch rows of x and of the f32 output (k_mvn reads
+        // and writes the padded rows), nt + 1 caches (the last one the padded slots'), the
+        // slot -> position / sequence maps
+        const size_t xb = (size_t)cols * 4, yb = (size_t)ldy * 4;
+        float* xp = P.get<float>(kMaxBatch * xb);
+        float* yp = P.get<float>(kMaxBatch * yb);
+        float* yout = epi == EPI_QKV ? A->q_dev : A->y_dev;
+        uint16_t *kcp = nullptr, *vcp = nullptr;
+        if (epi == EPI_QKV) {
+            kcp = P.get<uint16_t>((size_t)(nt + 1) * kvl * 2);
+            vcp = P.get<uint16_t>((size_t)(nt + 1) * kvl * 2);
+        }
+        int hmap[2 * kMaxBatch];  // [0, 8): positions, [8, 16): sequences
+        for (int t = 0; t < kMaxBatch; ++t) {
+            hmap[t] = t < nt && A->pos ? A->pos[t] : 0;
+            hmap[kMaxBatch + t] = t < nt ? t : nt;
+        }
+        int* dmap = P.get<int>(sizeof(hmap));
+        e = e == hipSuccess ? P.err : e;
+        if (e == hipSuccess) e = hipMemcpy(dmap, hmap, sizeof(hmap), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(xp, A->x_dev, (size_t)nt * xb, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipMemcpy(yp, yout, (size_t)nt * yb, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && kcp) e = hipMemcpy(kcp, A->kc_dev, (size_t)nt * kvl * 2, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && vcp) e = hipMemcpy(vcp, A->vc_dev, (size_t)nt * kvl * 2, hipMemcpyDeviceToDevice);
+        for (int g = 0; g < ng; ++g) {
+            MVArgs& a = grp[g];
+            a.x = xp; a.x_stride = cols; a.y = yp; a.y_stride = ldy; a.st = st;
+            a.tpos = dmap; a.tseq = dmap + kMaxBatch; a.kv_stride = kvl; a.kc = kcp; a.vc = vcp;
+        }
+        if (kernel == 1) {
+            for (int g = 0; g < ng && e == hipSuccess; ++g) e = launch_mvn(grp[g], epi, nt, mb, nullptr);
+        } else {
+            QuantScratch q(P, 64, (size_t)cols);
+            if (e == hipSuccess) e = P.err;
+            if (e == hipSuccess)
+                e = launch_pf_quant(xp, cols, A->norm_w_dev, A->eps, cols, 0, nt, q.aq, q.abs, q.ad, q.abf, nullptr, num ? 1 : 0);
+            if (kernel == 2) {
+                for (int g = 0; g < ng && e == hipSuccess; ++g) e = launch_bmm(grp[g], epi, nt, q.aq, q.abf, q.ad, nullptr);
+            } else if (e == hipSuccess) {
+                e = launch_bmm_qkv2(grp[0], grp[1], nt, q.aq, q.abf, q.ad, nullptr);
+                if (e == hipErrorNotSupported) {
+                    refused = "launch_bmm_qkv2 does not take this pair of types (or LLMI_BMM2 / LLMI_BMM_DMA is 0)";
+                    e = hipSuccess;
+                }
+            }
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess && !refused) e = hipMemcpy(yout, yp, (size_t)nt * yb, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && !refused && kcp) e = hipMemcpy(A->kc_dev, kcp, (size_t)nt * kvl * 2, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && !refused && vcp) e = hipMemcpy(A->vc_dev, vcp, (size_t)nt * kvl * 2, hipMemcpyDeviceToDevice);
+    }
+    if (refused) return bad(refused);
+    if (e == hipSuccess && epi == EPI_LOGITS) {
+        e = hipMemcpy(hs.data(), st, hs.size() * sizeof(StepState), hipMemcpyDeviceToHost);
+        for (int t = 0; t < nt && e == hipSuccess; ++t) {
+            A->token_out[t] = key_token(hs[(size_t)t].key[A->pos[t] & 1]);
+            A->pos_next_out[t] = hs[(size_t)t].pos_next;
+        }
+    }
+    if (e != hipSuccess) { set_err(std::string("llmi_mv_epilogue: ") + hip_err(e)); return -2; }
+    return 0;
+    API_CATCH(-5)
+}
+
 int32_t llmi_quantize_act(int32_t type, int64_t cols, const float* x, const float* nw, float eps, void* out) {
     if (cols % 256) { set_err("cols must be a multiple of 256"); return -1; }
     MVArgs a;

@@ -644,21 +644,15 @@ bool step_enqueue(Context& c, int kv_bound, std::string& err) {
         a.kc = c.kc + l * kv_layer; a.vc = c.vc + l * kv_layer; a.rope = c.rope; a.st = c.st;
         a.head_dim = D; a.n_rot = hp.n_rot; a.n_ctx = c.n_ctx; a.nq = nq; a.nk = nk;
         const Seg qkv[3] = {seg_of(m, L.wq, 0), seg_of(m, L.wk, nq), seg_of(m, L.wv, nq + nk)};
-        int i = 0, n = 0;
-        while (i < 3) {
-            int j = i;
-            a.nseg = 0;
-            int rows = 0;
-            while (j < 3 && act_kind(qkv[j].type) == act_kind(qkv[i].type)) { a.seg[a.nseg++] = qkv[j]; rows += qkv[j].rows; ++j; }
-            a.npairs = rows / 2;
+        int first[3];
+        const int n = qkv_launch_groups(qkv, true, a, out, first);
+        for (int g = 0; g < n; ++g) {
             double b = 8.0 * E;
-            for (int k = i; k < j; ++k) {
+            for (int k = first[g]; k < first[g] + out[g].nseg; ++k) {
                 const DevMat& dm = k == 0 ? L.wq : k == 1 ? L.wk : L.wv;
                 b += (double)dm.bytes + (k == 0 ? 4.0 * nq : 2.0 * nk);
             }
-            out[n] = a;
-            bytes[n++] = b;
-            i = j;
+            bytes[g] = b;
         }
         return n;
     };
@@ -851,19 +845,12 @@ static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std
         // groups in one k_bmd2 launch (launch_bmm_qkv2) on the matrix cores
         const Seg qkv[3] = {seg_of(m, L.wq, 0), seg_of(m, L.wk, QD), seg_of(m, L.wv, QD + nk)};
         MVArgs grp[3];
-        int ng = 0;
-        for (int i = 0; i < 3;) {
-            int j = i;
-            MVArgs a = base;
-            a.nseg = 0;
-            int rows = 0;
-            while (j < 3 && qkv[j].type == qkv[i].type) { a.seg[a.nseg++] = qkv[j]; rows += qkv[j].rows; ++j; }
-            a.cols = E; a.x = c.bx; a.x_stride = E; a.nw = (const float*)(m.arena + L.attn_norm.off_a); a.eps = hp.eps;
-            a.y = c.bq; a.y_stride = QD; a.kc = c.kc0 + l * kv_layer; a.vc = c.vc0 + l * kv_layer; a.rope = c.rope;
-            a.head_dim = D; a.n_rot = hp.n_rot; a.n_ctx = c.n_ctx; a.nq = QD; a.nk = nk; a.npairs = rows / 2;
-            grp[ng++] = a;
-            i = j;
-        }
+        int first[3];
+        MVArgs a = base;
+        a.cols = E; a.x = c.bx; a.x_stride = E; a.nw = (const float*)(m.arena + L.attn_norm.off_a); a.eps = hp.eps;
+        a.y = c.bq; a.y_stride = QD; a.kc = c.kc0 + l * kv_layer; a.vc = c.vc0 + l * kv_layer; a.rope = c.rope;
+        a.head_dim = D; a.n_rot = hp.n_rot; a.n_ctx = c.n_ctx; a.nq = QD; a.nk = nk;
+        const int ng = qkv_launch_groups(qkv, false, a, grp, first);
         bool done = false;
         if (ng == 2 && nt >= bmm_min_tokens() && bmm_ok(grp[0], EPI_QKV) && bmm_ok(grp[1], EPI_QKV)) {
             BC(launch_pf_quant(c.bx, E, grp[0].nw, hp.eps, E, 0, nt, c.baq, c.babs, c.bad, c.babf, c.stream, x86 ? 1 : 0));

@@ -262,6 +262,27 @@ hipError_t mv_split_launch(const MVArgs& a, int epi, int nt, hipStream_t s);
 template <int X86, int US>
 hipError_t mv_split_qkv2_launch(const MVArgs& a, int nt, hipStream_t s);
 
+// The QKV launches of a step: the runs of consecutive q / k / v segments of one activation
+// kind (by_act: the decode step, launch_matvec) or of one weight type (the batched step,
+// launch_mvn / launch_bmm).  out[g] = base with the run's segments and row pairs, first[g]
+// = the run's first segment; returns the number of runs.  (The step builders and the
+// llmi_mv_epilogue hook share it, so the hook launches what a step launches.)
+inline int qkv_launch_groups(const Seg (&qkv)[3], bool by_act, const MVArgs& base, MVArgs (&out)[3], int (&first)[3]) {
+    auto key = [&](const Seg& s) { return by_act ? act_kind(s.type) : s.type; };
+    int n = 0;
+    for (int i = 0; i < 3;) {
+        MVArgs a = base;
+        a.nseg = 0;
+        int j = i, rows = 0;
+        while (j < 3 && key(qkv[j]) == key(qkv[i])) { a.seg[a.nseg++] = qkv[j]; rows += qkv[j].rows; ++j; }
+        a.npairs = rows / 2;
+        first[n] = i;
+        out[n++] = a;
+        i = j;
+    }
+    return n;
+}
+
 // All launches are asynchronous on `stream` and graph-capturable (no allocation, no sync).
 hipError_t launch_matvec(const MVArgs& a, int epi, int max_blocks, hipStream_t stream);
 // generic-numerics attention path for a KV bound, 1..7 (listed at the top of attn.hip)

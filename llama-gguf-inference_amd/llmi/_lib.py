@@ -52,6 +52,36 @@ class llama_batch(C.Structure):
     ]
 
 
+class llmi_epilogue_args(C.Structure):
+    """llmi_mv_epilogue's arguments (include/llmi.h): device pointers as integers, `pos`,
+    `token_out` and `pos_next_out` host int32 arrays."""
+    _fields_ = [
+        ("kernel", C.c_int32),
+        ("epi", C.c_int32),
+        ("type", C.c_int32 * 3),
+        ("w_dev", C.c_void_p * 3),
+        ("rows", C.c_int64 * 3),
+        ("cols", C.c_int64),
+        ("x_dev", C.c_void_p),
+        ("norm_w_dev", C.c_void_p),
+        ("eps", C.c_float),
+        ("nt", C.c_int32),
+        ("pos", C.POINTER(C.c_int32)),
+        ("head_dim", C.c_int32),
+        ("n_rot", C.c_int32),
+        ("n_ctx", C.c_int32),
+        ("rope_dev", C.c_void_p),
+        ("q_dev", C.c_void_p),
+        ("kc_dev", C.c_void_p),
+        ("vc_dev", C.c_void_p),
+        ("y_dev", C.c_void_p),
+        ("token_out", C.POINTER(C.c_int32)),
+        ("pos_next_out", C.POINTER(C.c_int32)),
+    ]
+
+
+EPI_QKV, EPI_SWIGLU, EPI_LOGITS = 2, 3, 4  # LLMI_EPI_*
+
 # name -> (restype, argtypes); every entry point declared in include/llmi.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -140,6 +170,7 @@ SIGNATURES = {
     "llmi_repack": (C.c_int32, [C.c_int32, _P, _P, C.c_int64, C.c_int64]),
     "llmi_matvec": (C.c_int32, [C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, _P, C.c_int32]),
     "llmi_bmv": (C.c_int32, [C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_int32, _P, C.c_int32]),
+    "llmi_mv_epilogue": (C.c_int32, [C.POINTER(llmi_epilogue_args)]),
     "llmi_quantize_act": (C.c_int32, [C.c_int32, C.c_int64, _P, _P, C.c_float, _P]),
     "llmi_bench_stream": (C.c_double, [_P, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
     "llmi_bench_matvec": (C.c_double, [C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32]),
