@@ -753,7 +753,6 @@ int attn_path(int n_head, int n_head_kv, int kv_bound, int head_dim, int mode) {
     const int m = mode < 0 ? g_attn_mode : mode;
     const bool split_ok = (size_t)g * kv_bound * 4 <= kSplitAttnMaxLds;
     const bool fused_ok = kv_bound <= kFusedAttnMaxKV;
-    (void)n_head;
     if (m == 4 && g <= 8 && kv_bound <= kXAttnMaxKV) return 4;
     if (m == 5 && kv_bound <= kRegAttnMaxKV) return 5;
     if (m == 6 && kv_bound <= kDimAttnMaxKV) return 6;

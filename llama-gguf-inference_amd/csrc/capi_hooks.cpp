@@ -13,6 +13,104 @@
 
 using namespace llmi;
 
+namespace {
+// the device allocations of one hook call, freed on every way out; after a failure every
+// further request returns null and `err` keeps the first error
+struct DevPool {
+    std::vector<void*> all;
+    hipError_t err = hipSuccess;
+    template <class T>
+    T* get(size_t bytes, bool zero = true) {
+        void* p = nullptr;
+        if (err == hipSuccess) err = hipMalloc(&p, bytes ? bytes : 1);
+        if (err != hipSuccess) return nullptr;
+        all.push_back(p);
+        if (zero) err = hipMemset(p, 0, bytes);
+        return (T*)p;
+    }
+    ~DevPool() {
+        for (void* p : all) (void)hipFree(p);
+    }
+};
+// launch_pf_quant's outputs for tpad token rows (llmi_pf_gemm's sizes), zeroed: the padded
+// rows are read
+struct QuantScratch {
+    void* aq = nullptr;
+    int16_t* abs = nullptr;
+    float* ad = nullptr;
+    void* abf = nullptr;
+    QuantScratch(DevPool& P, size_t tpad, size_t cols) {
+        aq = P.get<void>(tpad * cols * 2);
+        abf = P.get<void>(tpad * (cols / 256) * 64);
+        abs = P.get<int16_t>(tpad * (cols / 16) * 2);
+        ad = P.get<float>(tpad * (cols / 32) * 4);
+    }
+};
+// the stream, event pair and graph exec of one hook call, destroyed on every way out
+struct HipObjs {
+    hipStream_t s = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipGraphExec_t ex = nullptr;
+    hipError_t events() {
+        const hipError_t e = e0 ? hipSuccess : hipEventCreate(&e0);
+        return e != hipSuccess || e1 ? e : hipEventCreate(&e1);
+    }
+    ~HipObjs() {
+        if (ex) (void)hipGraphExecDestroy(ex);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+// microseconds of what `launch` puts on the null stream, between two events
+template <class F>
+hipError_t time_launch(HipObjs& h, F launch, double& us) {
+    hipError_t e = h.events();
+    if (e != hipSuccess) return e;
+    (void)hipEventRecord(h.e0, nullptr);
+    e = launch();
+    (void)hipEventRecord(h.e1, nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(h.e1);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, h.e0, h.e1);
+    us = (double)ms * 1e3;
+    return e;
+}
+// microseconds per launch of h.ex (per_replay launches each) on h.s: one warm replay (code,
+// TLB), then n timed ones; < 0 on error
+double replay_us(HipObjs& h, int n, int per_replay) {
+    if (h.events() != hipSuccess) return -1.0;
+    (void)hipGraphLaunch(h.ex, h.s);
+    (void)hipEventRecord(h.e0, h.s);
+    for (int r = 0; r < n; ++r) (void)hipGraphLaunch(h.ex, h.s);
+    (void)hipEventRecord(h.e1, h.s);
+    float ms = 0.f;
+    if (hipEventSynchronize(h.e1) != hipSuccess || hipEventElapsedTime(&ms, h.e0, h.e1) != hipSuccess) return -1.0;
+    return (double)ms * 1e3 / ((double)n * per_replay);
+}
+bool head_shape_ok(int n_head, int n_head_kv, int head_dim) {
+    return n_head > 0 && n_head_kv > 0 && n_head % n_head_kv == 0 && (head_dim == 64 || head_dim == 128);
+}
+bool weight_type_ok(int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0; }
+int hook_grid_cap() {  // the matvec grid cap a context of the current device launches with
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return mv_grid_cap(dev);
+}
+// the StepStates of n steps at positions n_kv[t] - 1 (step sequence number seq), on the device
+StepState* dev_states(DevPool& P, const int* n_kv, int n, unsigned seq) {
+    std::vector<StepState> hs((size_t)n);
+    for (int t = 0; t < n; ++t) {
+        hs[(size_t)t].pos = n_kv[t] - 1;
+        hs[(size_t)t].pos_next = n_kv[t];
+        hs[(size_t)t].seq = seq;
+    }
+    StepState* st = P.get<StepState>((size_t)n * sizeof(StepState), false);
+    if (st) P.err = hipMemcpy(st, hs.data(), (size_t)n * sizeof(StepState), hipMemcpyHostToDevice);
+    return P.err == hipSuccess ? st : nullptr;
+}
+}  // namespace
+
 extern "C" {
 
 int32_t llmi_profile_kernels(struct llama_context* ctx, llama_token first, int32_t pos0, int32_t n_steps, double* us,
@@ -31,7 +129,7 @@ int32_t llmi_profile_kernels(struct llama_context* ctx, llama_token first, int32
     // (hipExtLaunchKernelGGL): each kernel's execution time in its real place in the
     // step (caches as its predecessor leaves them), without launch gaps.  One warm step
     // first.  No tokens are consumed: the state is reset to (first, pos0) afterwards.
-    const int kv_bound = std::min(c.n_ctx, (pos0 / 256 + 1) * 256);
+    const int kv_bound = kv_bucket_bound(pos0 + 1, c.n_ctx);
     std::string err;
     int rc = 0;
     {
@@ -84,7 +182,7 @@ int32_t llmi_engine_trace(struct llama_context* ctx, llama_token first, int32_t 
     const size_t n = (size_t)cus * 16 * 32;
     if ((size_t)n_out < n) { set_err("llmi_engine_trace: out holds fewer than CUs x 512 stamps"); return -1; }
     // one eager warm step, then one traced step at (first, pos0); the state is reset after
-    const int kv_bound = std::min(c.n_ctx, (pos0 / 256 + 1) * 256);
+    const int kv_bound = kv_bucket_bound(pos0 + 1, c.n_ctx);
     std::string err;
     int rc = 0;
     if (!c.le_trace && hipMalloc(&c.le_trace, n * 8) != hipSuccess) { set_err("llmi_engine_trace: hipMalloc"); return -3; }
@@ -171,8 +269,9 @@ int32_t llmi_debug_tap(struct llama_context* ctx, int32_t which, float* out) {
         return 0;
     }
     if (which == 0) {  // the last step's embedding row (get_rows), recomputed by k_embed's dequant
-        float* tmp = nullptr;
-        if (hipMalloc(&tmp, (size_t)hp.n_embd * 4) != hipSuccess) { set_err("out of device memory"); return -2; }
+        DevPool P;
+        float* tmp = P.get<float>((size_t)hp.n_embd * 4, false);
+        if (!tmp) { set_err("out of device memory"); return -2; }
         EmbArgs ea;
         ea.w = seg_of(*c.m, c.m->tok_embd, 0);
         ea.cols = hp.n_embd;
@@ -180,7 +279,6 @@ int32_t llmi_debug_tap(struct llama_context* ctx, int32_t which, float* out) {
         hipError_t e = launch_embed_row(ea, c.st, tmp, c.stream);
         if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, (size_t)hp.n_embd * 4, hipMemcpyDeviceToHost, c.stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-        (void)hipFree(tmp);
         if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
         return 0;
     }
@@ -241,7 +339,7 @@ int32_t llmi_repack(int32_t type, const void* raw, void* w, int64_t rows, int64_
 
 int32_t llmi_matvec(int32_t type, const void* w, int64_t rows, int64_t cols, const float* x, const float* nw, float eps,
                     float* y, int32_t mode) {
-    if (!(type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0) || cols % 256 || rows <= 0) {
+    if (!weight_type_ok(type) || cols % 256 || rows <= 0) {
         set_err("llmi_matvec: unsupported type/shape");
         return -1;
     }
@@ -252,11 +350,7 @@ int32_t llmi_matvec(int32_t type, const void* w, int64_t rows, int64_t cols, con
     a.npairs = (int)((rows + 1) / 2);
     a.x = x; a.nw = nw; a.eps = eps; a.y = y;
     a.num = t_hook_numerics & NUMERICS_X86;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    (void)hipGetDeviceProperties(&prop, dev);
-    hipError_t e = launch_matvec(a, mode == 1 ? EPI_ADD : EPI_STORE, std::max(64, prop.multiProcessorCount * wg_per_cu()), nullptr);
+    hipError_t e = launch_matvec(a, mode == 1 ? EPI_ADD : EPI_STORE, hook_grid_cap(), nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
     return 0;
@@ -265,45 +359,27 @@ int32_t llmi_matvec(int32_t type, const void* w, int64_t rows, int64_t cols, con
 int32_t llmi_pf_gemm(int32_t type, const void* w, int64_t rows, int64_t cols, const float* x, const float* nw, float eps,
                      int32_t n_tok, float* y, double* usec) {
     if (!pf_gemm_ok(type, (int)rows, (int)cols) || n_tok <= 0) { set_err("llmi_pf_gemm: unsupported type/shape"); return -1; }
+    API_TRY
     const int x86 = (t_hook_numerics & NUMERICS_X86) != 0;
-    const int tpad = (n_tok + 63) / 64 * 64;
-    void* aq = nullptr;
-    int16_t* abs = nullptr;
-    float* ad = nullptr;
-    void* abf = nullptr;
-    hipError_t e = hipMalloc(&aq, (size_t)tpad * cols * 2);
-    if (e == hipSuccess) e = hipMalloc(&abf, (size_t)tpad * (cols / 256) * 64);
-    if (e == hipSuccess) e = hipMemset(abf, 0, (size_t)tpad * (cols / 256) * 64);
-    if (e == hipSuccess) e = hipMalloc(&abs, (size_t)tpad * (cols / 16) * 2);
-    if (e == hipSuccess) e = hipMalloc(&ad, (size_t)tpad * (cols / 32) * 4);
-    if (e == hipSuccess) e = hipMemset(aq, 0, (size_t)tpad * cols * 2);
-    if (e == hipSuccess) e = hipMemset(abs, 0, (size_t)tpad * (cols / 16) * 2);
-    if (e == hipSuccess) e = hipMemset(ad, 0, (size_t)tpad * (cols / 32) * 4);
-    if (e == hipSuccess) e = launch_pf_quant(x, (int)cols, nw, eps, (int)cols, act_kind(type), n_tok, aq, abs, ad, abf, nullptr, x86);
+    DevPool P;
+    QuantScratch q(P, (size_t)(n_tok + 63) / 64 * 64, (size_t)cols);
+    hipError_t e = P.err;
+    if (e == hipSuccess) e = launch_pf_quant(x, (int)cols, nw, eps, (int)cols, act_kind(type), n_tok, q.aq, q.abs, q.ad, q.abf, nullptr, x86);
     PfGemm g;
     g.w = seg_at(type, w, rows, cols); g.rows = (int)rows; g.cols = (int)cols; g.T = n_tok;
-    g.aq = aq; g.abs = abs; g.ad = ad; g.abf = abf; g.y = y; g.ldy = (int)rows;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e == hipSuccess && usec) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, nullptr); }
-    if (e == hipSuccess) e = launch_pf_gemm(g, EPI_STORE, nullptr);
-    if (e == hipSuccess && usec) {
-        (void)hipEventRecord(e1, nullptr);
-        (void)hipEventSynchronize(e1);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *usec = ms * 1e3;
-    }
+    g.aq = q.aq; g.abs = q.abs; g.ad = q.ad; g.abf = q.abf; g.y = y; g.ldy = (int)rows;
+    HipObjs h;
+    auto launch = [&] { return launch_pf_gemm(g, EPI_STORE, nullptr); };
+    if (e == hipSuccess) e = usec ? time_launch(h, launch, *usec) : launch();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(aq); (void)hipFree(abs); (void)hipFree(ad); (void)hipFree(abf);
     if (e != hipSuccess) { set_err(hip_err(e)); return -2; }
     return 0;
+    API_CATCH(-5)
 }
 
 int32_t llmi_bmv(int32_t type, const void* w, int64_t rows, int64_t cols, const float* x, const float* nw, float eps,
                  int32_t nt, float* y, int32_t kernel) {
-    if (!(type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0) || rows <= 0 || rows > INT32_MAX ||
+    if (!weight_type_ok(type) || rows <= 0 || rows > INT32_MAX ||
         cols <= 0 || cols > INT32_MAX || cols % 256 || nt < 1 || nt > kMaxBatch || kernel < 0 || kernel > 1 || !w || !x ||
         !y) {
         set_err("llmi_bmv: bad arguments");
@@ -325,80 +401,27 @@ int32_t llmi_bmv(int32_t type, const void* w, int64_t rows, int64_t cols, const 
     }
     // k_mvn pads nt to 1, 2, 4 or 8 tokens and reads and writes the padded rows: both
     // sides go through kMaxBatch-row buffers of the hook's own, the x rows past nt zero
-    const size_t xb = (size_t)cols * 4, yb = (size_t)rows * 4, tpad = 64;
-    float *xp = nullptr, *yp = nullptr, *ad = nullptr;
-    void *aq = nullptr, *abf = nullptr;
-    int16_t* abs = nullptr;
-    hipError_t e = hipMalloc(&xp, kMaxBatch * xb);
-    if (e == hipSuccess) e = hipMalloc(&yp, kMaxBatch * yb);
-    if (e == hipSuccess) e = hipMemset(xp, 0, kMaxBatch * xb);
-    if (e == hipSuccess) e = hipMemset(yp, 0, kMaxBatch * yb);
+    const size_t xb = (size_t)cols * 4, yb = (size_t)rows * 4;
+    DevPool P;
+    float* xp = P.get<float>(kMaxBatch * xb);
+    float* yp = P.get<float>(kMaxBatch * yb);
+    hipError_t e = P.err;
     if (e == hipSuccess) e = hipMemcpy(xp, x, (size_t)nt * xb, hipMemcpyDeviceToDevice);
     a.x = xp; a.y = yp;
     if (e == hipSuccess && kernel == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        hipDeviceProp_t prop;
-        (void)hipGetDeviceProperties(&prop, dev);
-        e = launch_mvn(a, EPI_STORE, nt, std::max(64, prop.multiProcessorCount * wg_per_cu()), nullptr);
+        e = launch_mvn(a, EPI_STORE, nt, hook_grid_cap(), nullptr);
     } else if (e == hipSuccess) {  // the scratch of llmi_pf_gemm (a superset of the batched step's 32 rows)
-        e = hipMalloc(&aq, tpad * cols * 2);
-        if (e == hipSuccess) e = hipMalloc(&abf, tpad * (cols / 256) * 64);
-        if (e == hipSuccess) e = hipMalloc(&abs, tpad * (cols / 16) * 2);
-        if (e == hipSuccess) e = hipMalloc(&ad, tpad * (cols / 32) * 4);
-        if (e == hipSuccess) e = hipMemset(aq, 0, tpad * cols * 2);
-        if (e == hipSuccess) e = hipMemset(abf, 0, tpad * (cols / 256) * 64);
-        if (e == hipSuccess) e = hipMemset(abs, 0, tpad * (cols / 16) * 2);
-        if (e == hipSuccess) e = hipMemset(ad, 0, tpad * (cols / 32) * 4);
-        if (e == hipSuccess) e = launch_pf_quant(xp, (int)cols, nw, eps, (int)cols, 0, nt, aq, abs, ad, abf, nullptr, a.num ? 1 : 0);
-        if (e == hipSuccess) e = launch_bmm(a, EPI_STORE, nt, aq, abf, ad, nullptr);
+        QuantScratch q(P, 64, (size_t)cols);
+        e = P.err;
+        if (e == hipSuccess) e = launch_pf_quant(xp, (int)cols, nw, eps, (int)cols, 0, nt, q.aq, q.abs, q.ad, q.abf, nullptr, a.num ? 1 : 0);
+        if (e == hipSuccess) e = launch_bmm(a, EPI_STORE, nt, q.aq, q.abf, q.ad, nullptr);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(y, yp, (size_t)nt * yb, hipMemcpyDeviceToDevice);
-    (void)hipFree(xp); (void)hipFree(yp); (void)hipFree(aq); (void)hipFree(abf); (void)hipFree(abs); (void)hipFree(ad);
     if (e != hipSuccess) { set_err(std::string("llmi_bmv: ") + hip_err(e)); return -2; }
     return 0;
     API_CATCH(-5)
 }
-
-}  // extern "C"
-
-namespace {
-// the device allocations of one hook call, freed on every way out; after a failure every
-// further request returns null and `err` keeps the first error
-struct DevPool {
-    std::vector<void*> all;
-    hipError_t err = hipSuccess;
-    template <class T>
-    T* get(size_t bytes, bool zero = true) {
-        void* p = nullptr;
-        if (err == hipSuccess) err = hipMalloc(&p, bytes ? bytes : 1);
-        if (err != hipSuccess) return nullptr;
-        all.push_back(p);
-        if (zero) err = hipMemset(p, 0, bytes);
-        return (T*)p;
-    }
-    ~DevPool() {
-        for (void* p : all) (void)hipFree(p);
-    }
-};
-// launch_pf_quant's outputs for tpad token rows (llmi_pf_gemm's sizes), zeroed: the padded
-// rows are read
-struct QuantScratch {
-    void* aq = nullptr;
-    int16_t* abs = nullptr;
-    float* ad = nullptr;
-    void* abf = nullptr;
-    QuantScratch(DevPool& P, size_t tpad, size_t cols) {
-        aq = P.get<void>(tpad * cols * 2);
-        abf = P.get<void>(tpad * (cols / 256) * 64);
-        abs = P.get<int16_t>(tpad * (cols / 16) * 2);
-        ad = P.get<float>(tpad * (cols / 32) * 4);
-    }
-};
-}  // namespace
-
-extern "C" {
 
 int32_t llmi_mv_epilogue(const struct llmi_epilogue_args* A) {
     auto bad = [](const char* what) {
@@ -414,7 +437,7 @@ int32_t llmi_mv_epilogue(const struct llmi_epilogue_args* A) {
     const int nw = epi == EPI_QKV ? 3 : epi == EPI_SWIGLU ? 2 : 1;
     for (int i = 0; i < nw; ++i) {
         const int t = A->type[i];
-        if (!(t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0)) return bad("unknown weight type");
+        if (!weight_type_ok(t)) return bad("unknown weight type");
         if (!A->w_dev[i]) return bad("null weight");
         if (A->rows[i] <= 0 || A->rows[i] > INT32_MAX) return bad("rows out of range");
     }
@@ -502,11 +525,7 @@ int32_t llmi_mv_epilogue(const struct llmi_epilogue_args* A) {
     }
 
     DevPool P;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    (void)hipGetDeviceProperties(&prop, dev);
-    const int mb = std::max(64, prop.multiProcessorCount * wg_per_cu());
+    const int mb = hook_grid_cap();
     const size_t kvl = epi == EPI_QKV ? (size_t)(nk / D) * n_ctx * D : 0;  // elements of one cache
     // one StepState per token slot + the dummy one of the padded slots
     const int nslot = kernel == 0 || kernel == 3 ? 1 : nt;
@@ -540,35 +559,18 @@ int32_t llmi_mv_epilogue(const struct llmi_epilogue_args* A) {
         PfGemm g;
         g.T = T; g.cols = cols; g.aq = q.aq; g.abs = q.abs; g.ad = q.ad; g.abf = q.abf;
         if (epi == EPI_QKV) {
-            // prefill_enqueue's q / k / v loop, restated (there it is interleaved with the
-            // model's tensors): one quantization per activation kind, consecutive same-type
-            // parts (rows multiples of 64) in one launch
+            // prefill_enqueue's q / k / v launches (pf_qkv_launches)
             g.kc = A->kc_dev; g.vc = A->vc_dev; g.rope = A->rope_dev;
             g.pos0 = A->pos[0]; g.head_dim = D; g.n_rot = A->n_rot; g.n_ctx = n_ctx;
             g.y = A->q_dev; g.ldy = nq;
-            int quant_kind = -1;
-            for (int part = 0; part < 3 && e == hipSuccess;) {
-                if (act_kind(A->type[part]) != quant_kind) {
-                    quant_kind = act_kind(A->type[part]);
-                    e = launch_pf_quant(A->x_dev, cols, A->norm_w_dev, A->eps, cols, quant_kind, T, q.aq, q.abs, q.ad, q.abf,
+            PfGemm qg[3];
+            int qkind[3];
+            const int nqg = pf_qkv_launches(seg, g_pf_qkv_merge != 0, g, qg, qkind);
+            for (int i = 0; i < nqg && e == hipSuccess; ++i) {
+                if (qkind[i] >= 0)
+                    e = launch_pf_quant(A->x_dev, cols, A->norm_w_dev, A->eps, cols, qkind[i], T, q.aq, q.abs, q.ad, q.abf,
                                         nullptr, x86);
-                    if (e != hipSuccess) break;
-                }
-                int end = part + 1;
-                while (g_pf_qkv_merge && end < 3 && A->type[end] == A->type[part] && A->rows[end - 1] % 64 == 0) ++end;
-                g.w = seg[part]; g.w.row0 = 0; g.rows = (int)A->rows[part]; g.part = part; g.r1 = g.r2 = 0;
-                if (end > part + 1) {
-                    g.wk = seg[part + 1]; g.wk.row0 = 0;
-                    g.r1 = (int)A->rows[part];
-                    g.r2 = g.r1 + (int)A->rows[part + 1];
-                    g.rows = g.r2;
-                    if (end > part + 2) {
-                        g.wv = seg[part + 2]; g.wv.row0 = 0;
-                        g.rows += (int)A->rows[part + 2];
-                    }
-                }
-                e = launch_pf_gemm(g, EPI_QKV, nullptr);
-                part = end;
+                if (e == hipSuccess) e = launch_pf_gemm(qg[i], EPI_QKV, nullptr);
             }
         } else {  // gate into y, then y = silu(y) * up
             if (e == hipSuccess)
@@ -661,83 +663,56 @@ double llmi_bench_matvec_ex(int32_t type, const void* w, int32_t n_mats, int64_t
     const int64_t lb = llmi_device_layout_bytes(type, rows, cols);
     if (lb <= 0 || n_mats <= 0 || reps <= 0) { set_err("bad arguments"); return -1.0; }
     const size_t stride = align_up((size_t)lb, 4096);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    (void)hipGetDeviceProperties(&prop, dev);
-    const int mb = std::max(64, prop.multiProcessorCount * wg_per_cu());
-    float* nw = nullptr;
-    StepState* st = nullptr;
+    API_TRY
+    const int mb = hook_grid_cap();
     // mode bit 5: gate+up SwiGLU launch (rows = both halves; RMSNorm on), bit 6: residual-add
     // epilogue (ffn_down / attn_output)
     const bool swiglu = mode & 32, add = mode & 64;
     const bool norm = (mode & 1) || swiglu, logits = mode & 2, img = mode & 8;
+    DevPool P;
+    float* nw = norm ? P.get<float>((size_t)cols * 4, false) : nullptr;
+    StepState* st = logits ? P.get<StepState>(sizeof(StepState)) : nullptr;
+    // mode bit 3: timing with a pre-quantized activation image (zeros)
+    const uint8_t* xq = img ? P.get<uint8_t>((size_t)(cols / 256) * 304) : nullptr;
+    if (P.err != hipSuccess) { set_err("out of device memory"); return -1.0; }
     if (norm) {
         std::vector<float> ones((size_t)cols, 1.0f);
-        if (hipMalloc(&nw, (size_t)cols * 4) != hipSuccess) { set_err("out of device memory"); return -1.0; }
         (void)hipMemcpy(nw, ones.data(), (size_t)cols * 4, hipMemcpyHostToDevice);
     }
-    if (logits) {
-        if (hipMalloc(&st, sizeof(StepState)) != hipSuccess) { (void)hipFree(nw); set_err("out of device memory"); return -1.0; }
-        (void)hipMemset(st, 0, sizeof(StepState));
-    }
     MVArgs a;
-    a.nseg = 1; a.cols = (int)cols; a.npairs = (int)((rows + 1) / 2); a.x = x; a.y = y;
+    a.nseg = 1; a.cols = (int)cols; a.npairs = (int)((rows + 1) / 2); a.x = x; a.y = y; a.xq = xq;
     a.nw = nw; a.eps = 1e-5f; a.xfirst = (mode & 4) ? 1 : (mode & 256) ? -1 : 0;  // mode bit 2: weights after x, bit 8: never
-    if (mode & 16) a.prio_alt = prop.multiProcessorCount;  // mode bit 4 (experiment builds): alternating priority
-    if (logits) { a.st = st; a.argmax = &st->key[0][0]; }
-    uint8_t* xq = nullptr;  // mode bit 3: timing with a pre-quantized activation image (zeros)
-    if (img) {
-        if (hipMalloc(&xq, (size_t)(cols / 256) * 304) != hipSuccess) { set_err("out of device memory"); return -1.0; }
-        (void)hipMemset(xq, 0, (size_t)(cols / 256) * 304);
-        a.xq = xq;
+    if (mode & 16) {  // mode bit 4 (experiment builds): alternating priority, blocks past the CU count in the other phase
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&a.prio_alt, hipDeviceAttributeMultiprocessorCount, dev);
     }
+    if (logits) { a.st = st; a.argmax = &st->key[0][0]; }
     const int epi = logits ? EPI_LOGITS : swiglu ? EPI_SWIGLU : add ? EPI_ADD : EPI_STORE;
     const size_t half = swiglu ? (size_t)llmi_device_layout_bytes(type, rows / 2, cols) : 0;
     // one graph of n_mats launches (one per weight copy), replayed: no host launch cost
-    hipStream_t s = nullptr;
-    (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ex = nullptr;
-    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    HipObjs h;
+    (void)hipStreamCreateWithFlags(&h.s, hipStreamNonBlocking);
     // mode bit 7: every launch reads copy 0 (its weights L2/MALL-hot from the launch before)
     const size_t wstride = (mode & 128) ? 0 : stride;
-    for (int k = 0; ok && k < n_mats; ++k) {
-        if (swiglu) {
-            a.nseg = 2;
-            a.seg[0] = seg_at(type, (const uint8_t*)w + wstride * k, rows / 2, cols);
-            a.seg[1] = seg_at(type, (const uint8_t*)w + wstride * k + half, rows / 2, cols);
-        } else {
-            a.seg[0] = seg_at(type, (const uint8_t*)w + wstride * k, rows, cols);
+    std::string err;
+    h.ex = capture_graph(h.s, [&](std::string&) {
+        bool ok = true;
+        for (int k = 0; ok && k < n_mats; ++k) {
+            if (swiglu) {
+                a.nseg = 2;
+                a.seg[0] = seg_at(type, (const uint8_t*)w + wstride * k, rows / 2, cols);
+                a.seg[1] = seg_at(type, (const uint8_t*)w + wstride * k + half, rows / 2, cols);
+            } else {
+                a.seg[0] = seg_at(type, (const uint8_t*)w + wstride * k, rows, cols);
+            }
+            ok = launch_matvec(a, epi, mb, h.s) == hipSuccess;
         }
-        ok = launch_matvec(a, epi, mb, s) == hipSuccess;
-    }
-    ok = (hipStreamEndCapture(s, &g) == hipSuccess) && ok && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
-    double res = -1.0;
-    const int nrep = std::max(1, reps / n_mats);
-    if (ok) {
-        hipEvent_t e0, e1;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        (void)hipGraphLaunch(ex, s);  // warm-up (code, TLB)
-        (void)hipEventRecord(e0, s);
-        for (int r = 0; r < nrep; ++r) (void)hipGraphLaunch(ex, s);
-        (void)hipEventRecord(e1, s);
-        float ms = 0.f;
-        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
-            res = (double)ms * 1e3 / ((double)nrep * n_mats);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    } else {
-        set_err("llmi_bench_matvec: capture/launch failed");
-    }
-    if (ex) (void)hipGraphExecDestroy(ex);
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipStreamDestroy(s);
-    (void)hipFree(nw);
-    (void)hipFree(st);
-    (void)hipFree(xq);
-    return res;
+        return ok;
+    }, err);
+    if (!h.ex) { set_err("llmi_bench_matvec: capture/launch failed"); return -1.0; }
+    return replay_us(h, std::max(1, reps / n_mats), n_mats);
+    API_CATCH(-1.0)
 }
 
 double llmi_bench_matvec(int32_t type, const void* w, int32_t n_mats, int64_t rows, int64_t cols, const float* x, float* y,
@@ -746,22 +721,19 @@ double llmi_bench_matvec(int32_t type, const void* w, int32_t n_mats, int64_t ro
 }
 
 double llmi_bench_stream(const void* dev, int32_t n_bufs, uint64_t stride, uint64_t bytes, int32_t reps, int32_t blocks) {
-    unsigned* out = nullptr;
-    if (hipMalloc(&out, 16) != hipSuccess) return -1.0;
+    API_TRY
+    DevPool P;
+    unsigned* out = P.get<unsigned>(16, false);
+    if (!out) return -1.0;
     for (int k = 0; k < n_bufs; ++k) (void)launch_stream_read((const uint8_t*)dev + stride * k, bytes, out, blocks, nullptr);
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
-    hipEventRecord(e0, nullptr);
-    for (int r = 0; r < reps; ++r) (void)launch_stream_read((const uint8_t*)dev + stride * (r % n_bufs), bytes, out, blocks, nullptr);
-    hipEventRecord(e1, nullptr);
-    hipEventSynchronize(e1);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    (void)hipFree(out);
-    return (double)ms * 1e3 / reps;
+    HipObjs h;
+    double us = 0.0;
+    const hipError_t e = time_launch(h, [&] {
+        for (int r = 0; r < reps; ++r) (void)launch_stream_read((const uint8_t*)dev + stride * (r % n_bufs), bytes, out, blocks, nullptr);
+        return hipSuccess;
+    }, us);
+    return e == hipSuccess ? us / reps : -1.0;
+    API_CATCH(-1.0)
 }
 
 }  // extern "C"
@@ -773,38 +745,23 @@ double llmi_bench_stream(const void* dev, int32_t n_bufs, uint64_t stride, uint6
 // dependent-launch gap), < 0 on error.  mode: attention path (0 auto, 1 fused, 2 split, 3 two-kernel).
 int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_kv, int32_t n_ctx, const float* q,
                        const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode) {
-    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || n_kv <= 0 ||
-        n_ctx < n_kv || n_ctx % 256 || !q || !kc || !vc || !out) {
+    if (!head_shape_ok(n_head, n_head_kv, head_dim) || n_kv <= 0 || n_ctx < n_kv || n_ctx % 256 || !q || !kc || !vc || !out) {
         set_err("llmi_attention: bad arguments");
         return -1;
     }
     API_TRY
-    float* scores = nullptr;
-    StepState* st = nullptr;
-    if (hipMalloc(&scores, attn_scratch_floats(n_head, n_ctx) * 4) != hipSuccess || hipMalloc(&st, sizeof(StepState)) != hipSuccess) {
-        (void)hipFree(scores);
-        set_err("llmi_attention: out of device memory");
-        return -2;
-    }
-    StepState hs{};
-    hs.pos = n_kv - 1;
-    hs.pos_next = n_kv;
-    hs.seq = 1;
-    (void)hipMemcpy(st, &hs, sizeof(hs), hipMemcpyHostToDevice);
-    (void)hipMemset(scores, 0, attn_scratch_floats(n_head, n_ctx) * 4);
+    DevPool P;
+    float* scores = P.get<float>(attn_scratch_floats(n_head, n_ctx) * 4);
+    StepState* st = dev_states(P, &n_kv, 1, 1);
+    if (P.err != hipSuccess) { set_err("llmi_attention: out of device memory"); return -2; }
     AttnArgs a;
-    a.q = q; a.kc = kc; a.vc = vc; a.scores = scores; a.out = out; a.st = st; a.n_ctx = n_ctx;
+    a.q = q; a.kc = kc; a.vc = vc; a.out = out; a.st = st; a.n_ctx = n_ctx;
     a.scale = 1.0f / sqrtf((float)head_dim);
-    a.tmax = scores + (size_t)n_head * n_ctx;
-    a.gran = (unsigned long long*)(scores + attn_gran_off(n_head, n_ctx));
-    a.fault = (unsigned*)(scores + attn_gran_off(n_head, n_ctx) + 2 * (size_t)n_head * kXAttnMaxKV);
+    attn_bind_scratch(a, scores, n_head, n_ctx);
     a.num = t_hook_numerics & NUMERICS_X86;
     a.fa = (t_hook_numerics & NUMERICS_FA) ? 1 : 0;
-    const int kv_bound = std::min(n_ctx, (n_kv + 255) / 256 * 256);
-    hipError_t e = launch_attention(a, n_head, n_head_kv, head_dim, kv_bound, nullptr, mode);
+    hipError_t e = launch_attention(a, n_head, n_head_kv, head_dim, kv_bucket_bound(n_kv, n_ctx), nullptr, mode);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(scores);
-    (void)hipFree(st);
     if (e != hipSuccess) { set_err(std::string("llmi_attention: ") + hip_err(e)); return -3; }
     return 0;
     API_CATCH(-5)
@@ -813,8 +770,7 @@ int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
 // The decode attention path launch_attention takes for this shape, KV bound and mode (host
 // only: no device call, so a test can ask on a machine without a GPU).
 int32_t llmi_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t kv_bound, int32_t mode) {
-    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || kv_bound <= 0 ||
-        mode < 0 || mode > 7) {
+    if (!head_shape_ok(n_head, n_head_kv, head_dim) || kv_bound <= 0 || mode < 0 || mode > 7) {
         set_err("llmi_attn_path: bad arguments");
         return -1;
     }
@@ -832,8 +788,8 @@ int32_t llmi_attn_x86_form(int32_t kv_bound, int32_t mode) {
 // laid out as the batched step lays them out; the KV bound is the batch's (its longest slot).
 int32_t llmi_battention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t nt, const int32_t* n_kv, int32_t n_ctx,
                         const float* q, const uint16_t* kc, const uint16_t* vc, float* out) {
-    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || nt < 1 ||
-        nt > kMaxBatch || !n_kv || n_ctx <= 0 || n_ctx % 256 || !q || !kc || !vc || !out) {
+    if (!head_shape_ok(n_head, n_head_kv, head_dim) || nt < 1 || nt > kMaxBatch || !n_kv || n_ctx <= 0 || n_ctx % 256 || !q ||
+        !kc || !vc || !out) {
         set_err("llmi_battention: bad arguments");
         return -1;
     }
@@ -845,111 +801,85 @@ int32_t llmi_battention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int
     API_TRY
     const size_t scr = attn_scratch_floats(n_head, n_ctx);
     const size_t QD = (size_t)n_head * head_dim, kvl = (size_t)n_head_kv * n_ctx * head_dim;
-    float* scores = nullptr;
-    StepState* st = nullptr;
-    if (hipMalloc(&scores, (size_t)nt * scr * 4) != hipSuccess || hipMalloc(&st, (size_t)nt * sizeof(StepState)) != hipSuccess) {
-        (void)hipFree(scores);
-        set_err("llmi_battention: out of device memory");
-        return -2;
-    }
-    std::vector<StepState> hs((size_t)nt);
-    for (int t = 0; t < nt; ++t) {
-        hs[(size_t)t].pos = n_kv[t] - 1;
-        hs[(size_t)t].pos_next = n_kv[t];
-        hs[(size_t)t].seq = 1;
-    }
-    (void)hipMemcpy(st, hs.data(), (size_t)nt * sizeof(StepState), hipMemcpyHostToDevice);
-    (void)hipMemset(scores, 0, (size_t)nt * scr * 4);
+    DevPool P;
+    float* scores = P.get<float>((size_t)nt * scr * 4);
+    StepState* st = dev_states(P, n_kv, nt, 1);
+    if (P.err != hipSuccess) { set_err("llmi_battention: out of device memory"); return -2; }
     BAttnArgs ba;
     for (int t = 0; t < nt; ++t) {
         AttnArgs& at = ba.a[t];
         at.q = q + (size_t)t * QD; at.kc = kc + (size_t)t * kvl; at.vc = vc + (size_t)t * kvl;
-        at.scores = scores + (size_t)t * scr; at.tmax = at.scores + (size_t)n_head * n_ctx;
+        // (bstep_enqueue binds without the exchange path's granules: no batched path reads them)
+        attn_bind_scratch(at, scores + (size_t)t * scr, n_head, n_ctx);
         at.out = out + (size_t)t * QD; at.st = st + t; at.n_ctx = n_ctx;
         at.scale = 1.0f / sqrtf((float)head_dim);
-        // (the batched step leaves the exchange path's granules unset: no batched path reads them)
-        at.gran = (unsigned long long*)(at.scores + attn_gran_off(n_head, n_ctx));
-        at.fault = (unsigned*)(at.scores + attn_gran_off(n_head, n_ctx) + 2 * (size_t)n_head * kXAttnMaxKV);
         at.num = t_hook_numerics & NUMERICS_X86;
         at.fa = (t_hook_numerics & NUMERICS_FA) ? 1 : 0;
     }
-    const int kv_bound = std::min(n_ctx, (max_kv + 255) / 256 * 256);
-    hipError_t e = launch_battention(ba, nt, n_head, n_head_kv, head_dim, kv_bound, nullptr);
+    hipError_t e = launch_battention(ba, nt, n_head, n_head_kv, head_dim, kv_bucket_bound(max_kv, n_ctx), nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(scores);
-    (void)hipFree(st);
     if (e != hipSuccess) { set_err(std::string("llmi_battention: ") + hip_err(e)); return -3; }
     return 0;
     API_CATCH(-5)
 }
 
+// The three llmi_pf_attention* hooks after their own argument checks: one timed
+// launch_pf_attn over T rows at pos0.. (`at` brings the numerics and, for path 0, the score
+// scratch); microseconds, -3 on a launch error
+static double pf_attention_run(const char* name, PfAttn at, int n_head, int n_head_kv, int head_dim, int T, int pos0,
+                               int n_ctx, const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int path = -1) {
+    at.q = q; at.out = out; at.ldq = n_head * head_dim; at.kc = kc; at.vc = vc;
+    at.n_ctx = n_ctx; at.pos0 = pos0; at.gqa = n_head / n_head_kv; at.max_kv = pos0 + T;
+    at.scale = 1.0f / sqrtf((float)head_dim);
+    HipObjs h;
+    double us = 0.0;
+    hipError_t e = time_launch(h, [&] { return launch_pf_attn(at, n_head, head_dim, T, nullptr, path); }, us);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_err(std::string(name) + ": " + hip_err(e)); return -3; }
+    return us;
+}
+// the arguments the three hooks check alike
+static bool pf_attention_args_ok(int n_head, int n_head_kv, int head_dim, int T, int pos0, int n_ctx, const void* q,
+                                 const void* kc, const void* vc, const void* out) {
+    return head_shape_ok(n_head, n_head_kv, head_dim) && T > 0 && pos0 >= 0 && n_ctx % 256 == 0 && pos0 + T <= n_ctx && q &&
+           kc && vc && out;
+}
+
 double llmi_pf_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
                          const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode,
                          int64_t scratch_bytes) {
-    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || T <= 0 ||
-        pos0 < 0 || n_ctx % 256 || pos0 + T > n_ctx || pos0 + T > kPfAttnMaxKV || mode < 0 || mode > 2 || !q || !kc ||
-        !vc || !out) {
+    if (!pf_attention_args_ok(n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out) || pos0 + T > kPfAttnMaxKV ||
+        mode < 0 || mode > 2) {
         set_err("llmi_pf_attention: bad arguments");
         return -1;
     }
     API_TRY
     PfAttn at;
-    at.q = q; at.out = out; at.ldq = n_head * head_dim; at.kc = kc; at.vc = vc;
-    at.n_ctx = n_ctx; at.pos0 = pos0; at.gqa = n_head / n_head_kv; at.max_kv = pos0 + T;
-    at.scale = 1.0f / sqrtf((float)head_dim);
-    float* wsc = nullptr;
+    DevPool P;
     if (mode == 0) {
         size_t bytes = pf_fa_scratch_bytes(n_head, n_head_kv, head_dim, std::max(T, 512), n_ctx);
         if (!bytes) { set_err("llmi_pf_attention: no tiled kernel for this head shape"); return -1; }
         if (scratch_bytes > 0) bytes = (size_t)scratch_bytes;
-        if (hipMalloc(&wsc, bytes) != hipSuccess) { set_err("llmi_pf_attention: out of device memory"); return -2; }
-        at.wsc = wsc; at.wsc_bytes = bytes;
+        at.wsc = P.get<float>(bytes, false);
+        if (!at.wsc) { set_err("llmi_pf_attention: out of device memory"); return -2; }
+        at.wsc_bytes = bytes;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, nullptr);
-    hipError_t e = launch_pf_attn(at, n_head, head_dim, T, nullptr, mode);
-    (void)hipEventRecord(e1, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    float ms = 0.f;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(wsc);
-    if (e != hipSuccess) { set_err(std::string("llmi_pf_attention: ") + hip_err(e)); return -3; }
-    return (double)ms * 1e3;
+    return pf_attention_run("llmi_pf_attention", at, n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out, mode);
     API_CATCH(-5)
 }
 
 double llmi_pf_attention_fa(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
                             const float* q, const uint16_t* kc, const uint16_t* vc, float* out) {
-    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || n_head / n_head_kv > 32 ||
-        (head_dim != 64 && head_dim != 128) || T <= 0 || pos0 < 0 || n_ctx % 256 || pos0 + T > n_ctx ||
-        pos0 + T > kFaMaxKV || !q || !kc || !vc || !out) {
+    if (!pf_attention_args_ok(n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out) || n_head / n_head_kv > 32 ||
+        pos0 + T > kFaMaxKV) {
         set_err("llmi_pf_attention_fa: bad arguments");
         return -1;
     }
     API_TRY
     PfAttn at;
-    at.q = q; at.out = out; at.ldq = n_head * head_dim; at.kc = kc; at.vc = vc;
-    at.n_ctx = n_ctx; at.pos0 = pos0; at.gqa = n_head / n_head_kv; at.max_kv = pos0 + T;
-    at.scale = 1.0f / sqrtf((float)head_dim);
     at.num = t_hook_numerics & NUMERICS_X86;
     at.fa = 1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, nullptr);
-    hipError_t e = launch_pf_attn(at, n_head, head_dim, T, nullptr);
-    (void)hipEventRecord(e1, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    float ms = 0.f;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (e != hipSuccess) { set_err(std::string("llmi_pf_attention_fa: ") + hip_err(e)); return -3; }
-    return (double)ms * 1e3;
+    return pf_attention_run("llmi_pf_attention_fa", at, n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out);
     API_CATCH(-5)
 }
 
@@ -958,36 +888,20 @@ double llmi_pf_attention_fa(int32_t n_head, int32_t n_head_kv, int32_t head_dim,
 // pf_attn_x86_max_kv, a head shape without an instantiation) is an error here.
 double llmi_pf_attention_x86(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
                              const float* q, const uint16_t* kc, const uint16_t* vc, float* out) {
-    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || T <= 0 ||
-        pos0 < 0 || n_ctx % 256 || pos0 + T > n_ctx || pos0 + T > kPfAttnMaxKV || !q || !kc || !vc || !out) {
+    if (!pf_attention_args_ok(n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out) || pos0 + T > kPfAttnMaxKV) {
         set_err("llmi_pf_attention_x86: bad arguments");
         return -1;
     }
     API_TRY
     PfAttn at;
-    at.q = q; at.out = out; at.ldq = n_head * head_dim; at.kc = kc; at.vc = vc;
-    at.n_ctx = n_ctx; at.pos0 = pos0; at.gqa = n_head / n_head_kv; at.max_kv = pos0 + T;
-    at.scale = 1.0f / sqrtf((float)head_dim);
     at.num = NUMERICS_X86;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, nullptr);
-    hipError_t e = launch_pf_attn(at, n_head, head_dim, T, nullptr);
-    (void)hipEventRecord(e1, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    float ms = 0.f;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (e != hipSuccess) { set_err(std::string("llmi_pf_attention_x86: ") + hip_err(e)); return -3; }
-    return (double)ms * 1e3;
+    return pf_attention_run("llmi_pf_attention_x86", at, n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out);
     API_CATCH(-5)
 }
 
 // The longest KV k_pf_a86 takes for this head shape (host only: no device call).
 int32_t llmi_pf_attn_x86_max_kv(int32_t n_head, int32_t n_head_kv, int32_t head_dim) {
-    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128)) {
+    if (!head_shape_ok(n_head, n_head_kv, head_dim)) {
         set_err("llmi_pf_attn_x86_max_kv: bad arguments");
         return -1;
     }
@@ -996,44 +910,31 @@ int32_t llmi_pf_attn_x86_max_kv(int32_t n_head, int32_t n_head_kv, int32_t head_
 
 double llmi_bench_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_kv, int32_t mode, int32_t reps,
                             uint64_t* trace_dev) {
-    if (n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || (head_dim != 64 && head_dim != 128) || n_kv <= 0 || reps <= 0) {
+    if (!head_shape_ok(n_head, n_head_kv, head_dim) || n_kv <= 0 || reps <= 0) {
         set_err("llmi_bench_attention: bad arguments");
         return -1.0;
     }
-    const int n_ctx = (n_kv + 255) / 256 * 256;
+    API_TRY
+    const int kv_bound = kv_bucket_bound(n_kv, INT32_MAX), n_ctx = kv_bound;
     const size_t kv_layer = (size_t)n_head_kv * n_ctx * head_dim;  // elements per layer, K or V
     const int nl = (int)std::max<size_t>(2, (size_t)(512u << 20) / (kv_layer * 4) + 1);
-    uint16_t *kc = nullptr, *vc = nullptr;
-    float *q = nullptr, *scores = nullptr, *out = nullptr;
-    StepState* st = nullptr;
-    auto cleanup = [&] {
-        (void)hipFree(kc); (void)hipFree(vc); (void)hipFree(q); (void)hipFree(scores); (void)hipFree(out); (void)hipFree(st);
-    };
-    if (hipMalloc(&kc, kv_layer * nl * 2) != hipSuccess || hipMalloc(&vc, kv_layer * nl * 2) != hipSuccess ||
-        hipMalloc(&q, (size_t)n_head * head_dim * 4) != hipSuccess ||
-        hipMalloc(&scores, attn_scratch_floats(n_head, n_ctx) * 4) != hipSuccess ||
-        hipMalloc(&out, (size_t)n_head * head_dim * 4) != hipSuccess || hipMalloc(&st, sizeof(StepState)) != hipSuccess) {
-        cleanup();
-        set_err("llmi_bench_attention: out of device memory");
-        return -1.0;
-    }
+    DevPool P;
+    uint16_t* kc = P.get<uint16_t>(kv_layer * nl * 2, false);
+    uint16_t* vc = P.get<uint16_t>(kv_layer * nl * 2, false);
+    float* q = P.get<float>((size_t)n_head * head_dim * 4);
+    float* scores = P.get<float>(attn_scratch_floats(n_head, n_ctx) * 4);
+    float* out = P.get<float>((size_t)n_head * head_dim * 4, false);
+    StepState* st = dev_states(P, &n_kv, 1, 0);
+    if (P.err != hipSuccess) { set_err("llmi_bench_attention: out of device memory"); return -1.0; }
     (void)hipMemset(kc, 0x3c, kv_layer * nl * 2);  // f16 0x3c3c ~ 1.06
     (void)hipMemset(vc, 0x3c, kv_layer * nl * 2);
-    (void)hipMemset(q, 0, (size_t)n_head * head_dim * 4);
-    StepState hs{};
-    hs.pos = n_kv - 1;
-    hs.pos_next = n_kv;
-    (void)hipMemcpy(st, &hs, sizeof(hs), hipMemcpyHostToDevice);
-    hipStream_t s = nullptr;
-    (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    const int kv_bound = std::min(n_ctx, (n_kv + 255) / 256 * 256);
+    HipObjs h;
+    (void)hipStreamCreateWithFlags(&h.s, hipStreamNonBlocking);
+    const hipStream_t s = h.s;
     AttnArgs a;
-    a.q = q; a.scores = scores; a.out = out; a.st = st; a.n_ctx = n_ctx; a.scale = 1.0f / sqrtf((float)head_dim);
+    a.q = q; a.out = out; a.st = st; a.n_ctx = n_ctx; a.scale = 1.0f / sqrtf((float)head_dim);
     a.num = t_hook_numerics & NUMERICS_X86;
-    a.tmax = scores + (size_t)n_head * n_ctx;
-    a.gran = (unsigned long long*)(scores + attn_gran_off(n_head, n_ctx));
-    a.fault = (unsigned*)(scores + attn_gran_off(n_head, n_ctx) + 2 * (size_t)n_head * kXAttnMaxKV);
-    (void)hipMemset(scores, 0, attn_scratch_floats(n_head, n_ctx) * 4);
+    attn_bind_scratch(a, scores, n_head, n_ctx);
     if (trace_dev) {  // one traced eager launch on a cold layer (LLMI_EXP_TRACE builds)
         for (int l = 0; l + 1 < nl; ++l) {
             a.kc = kc + (size_t)l * kv_layer;
@@ -1047,44 +948,23 @@ double llmi_bench_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim,
         a.trace = (unsigned long long*)trace_dev;
         const bool okt = launch_attention(a, n_head, n_head_kv, head_dim, kv_bound, s, mode) == hipSuccess &&
                          hipStreamSynchronize(s) == hipSuccess;
-        (void)hipStreamDestroy(s);
-        cleanup();
         return okt ? 0.0 : -1.0;
     }
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ex = nullptr;
-    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    // a new step sequence number per replay: k_attn_x's hand-off tags never repeat
-    ok = ok && launch_state_tick(st, s) == hipSuccess;
-    for (int l = 0; ok && l < nl; ++l) {
-        a.kc = kc + (size_t)l * kv_layer;
-        a.vc = vc + (size_t)l * kv_layer;
-        a.layer = l % 255;
-        ok = launch_attention(a, n_head, n_head_kv, head_dim, kv_bound, s, mode) == hipSuccess;
-    }
-    ok = (hipStreamEndCapture(s, &g) == hipSuccess) && ok && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
-    double res = -1.0;
-    if (ok) {
-        hipEvent_t e0, e1;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        (void)hipGraphLaunch(ex, s);
-        (void)hipEventRecord(e0, s);
-        for (int r = 0; r < reps; ++r) (void)hipGraphLaunch(ex, s);
-        (void)hipEventRecord(e1, s);
-        float ms = 0.f;
-        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
-            res = (double)ms * 1e3 / ((double)reps * nl);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    } else {
-        set_err("llmi_bench_attention: capture/launch failed");
-    }
-    if (ex) (void)hipGraphExecDestroy(ex);
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipStreamDestroy(s);
-    cleanup();
-    return res;
+    std::string err;
+    h.ex = capture_graph(s, [&](std::string&) {
+        // a new step sequence number per replay: k_attn_x's hand-off tags never repeat
+        bool ok = launch_state_tick(st, s) == hipSuccess;
+        for (int l = 0; ok && l < nl; ++l) {
+            a.kc = kc + (size_t)l * kv_layer;
+            a.vc = vc + (size_t)l * kv_layer;
+            a.layer = l % 255;
+            ok = launch_attention(a, n_head, n_head_kv, head_dim, kv_bound, s, mode) == hipSuccess;
+        }
+        return ok;
+    }, err);
+    if (!h.ex) { set_err("llmi_bench_attention: capture/launch failed"); return -1.0; }
+    return replay_us(h, reps, nl);
+    API_CATCH(-1.0)
 }
 
 // Experiment hook (LLMI_EXP_TRACE builds): one STORE matvec launch with per-wave
@@ -1092,26 +972,20 @@ double llmi_bench_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim,
 // written to trace_dev[grid*waves*6]; returns the grid size, < 0 on error.
 int32_t llmi_trace_matvec(int32_t type, const void* w, int64_t rows, int64_t cols, const float* x, float* y, int32_t mode,
                           uint64_t* trace_dev) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    (void)hipGetDeviceProperties(&prop, dev);
-    const int mb = std::max(64, prop.multiProcessorCount * wg_per_cu());
+    API_TRY
+    const int mb = hook_grid_cap();
     MVArgs a;
     a.nseg = 1; a.cols = (int)cols; a.npairs = (int)((rows + 1) / 2); a.x = x; a.y = y;
     a.seg[0] = seg_at(type, w, rows, cols);
     a.trace = (unsigned long long*)trace_dev;
     if (mode & 256) a.xfirst = -1;  // mode bit 8: weights issued before the activation arrives
-    uint8_t* xq = nullptr;  // mode bit 3: pre-quantized activation image (zeros)
-    if ((mode & 8) && hipMalloc(&xq, (size_t)(cols / 256) * 304) == hipSuccess) {
-        (void)hipMemset(xq, 0, (size_t)(cols / 256) * 304);
-        a.xq = xq;
-    }
+    DevPool P;
+    if (mode & 8) a.xq = P.get<uint8_t>((size_t)(cols / 256) * 304);  // mode bit 3: pre-quantized activation image (zeros)
     const bool ok = launch_matvec(a, EPI_STORE, mb, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-    (void)hipFree(xq);
     if (!ok) {
         set_err("llmi_trace_matvec: launch failed");
         return -1;
     }
     return std::min(mb, (a.npairs + kMVWaves - 1) / kMVWaves);
+    API_CATCH(-1)
 }

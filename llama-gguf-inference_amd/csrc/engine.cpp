@@ -26,6 +26,30 @@ int wg_per_cu() {  // read per call (context creation): tests vary it within a p
     return n > 0 ? n : 2;
 }
 
+int mv_grid_cap(int device) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
+    return std::max(64, cus * wg_per_cu());
+}
+
+hipGraphExec_t capture_graph(hipStream_t s, const std::function<bool(std::string&)>& enqueue, std::string& err) {
+    hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) { err = "hipStreamBeginCapture: " + hip_err(e); return nullptr; }
+    std::string e2;
+    const bool ok = enqueue(e2);
+    hipGraph_t g = nullptr;
+    hipGraphExec_t ex = nullptr;
+    e = hipStreamEndCapture(s, &g);
+    if (!ok) err = "capture: " + e2;
+    else if (e != hipSuccess) err = "hipStreamEndCapture: " + hip_err(e);
+    else if ((e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0)) != hipSuccess) {
+        err = "hipGraphInstantiate: " + hip_err(e);
+        ex = nullptr;
+    }
+    if (g) (void)hipGraphDestroy(g);
+    return ex;
+}
+
 #define HIPC(expr)                                                         \
     do {                                                                   \
         hipError_t e_ = (expr);                                            \
@@ -399,9 +423,7 @@ bool context_init(Model* m, int n_ctx, bool use_graphs, int n_seq, Context& c, s
     }
     c.use_graphs = use_graphs;
     HIPC(hipSetDevice(m->device));
-    hipDeviceProp_t prop;
-    HIPC(hipGetDeviceProperties(&prop, m->device));
-    c.max_blocks = std::max(64, prop.multiProcessorCount * wg_per_cu());
+    if (!(c.max_blocks = mv_grid_cap(m->device))) { err = "device query failed"; return false; }
     HIPC(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     HIPC(hipEventCreate(&c.ev0));
     HIPC(hipEventCreate(&c.ev1));
@@ -413,7 +435,11 @@ bool context_init(Model* m, int n_ctx, bool use_graphs, int n_seq, Context& c, s
     HIPC(hipMalloc(&c.h, (size_t)hp.n_ff * 4));
     HIPC(hipMalloc(&c.logits, (size_t)hp.n_vocab * 4));
     HIPC(hipMalloc(&c.scores, attn_scratch_floats(hp.n_head, c.n_ctx) * 4));
-    c.fault_dev = (unsigned*)(c.scores + attn_gran_off(hp.n_head, c.n_ctx) + 2 * (size_t)hp.n_head * kXAttnMaxKV);
+    {
+        AttnArgs a;
+        attn_bind_scratch(a, c.scores, hp.n_head, c.n_ctx);
+        c.fault_dev = a.fault;
+    }
     HIPC(hipHostMalloc((void**)&c.fault_host, 16, hipHostMallocDefault));
     HIPC(hipMalloc(&c.le_cnt, le_counter_bytes(hp.n_layer)));
     *c.fault_host = 0;
@@ -460,14 +486,20 @@ void context_select_seq(Context& c, int s) {
     if (s < (int)c.seq_past.size()) c.n_past = c.seq_past[(size_t)s];
 }
 
+// a sequence's state before its first step: no token fed from the host
+static StepState fresh_step_state() {
+    StepState s{};
+    s.token_in = -1;
+    s.token_in_pos = -1;
+    return s;
+}
+
 void context_clear_seq(Context& c, int s) {
     (void)hipSetDevice(c.device);
     (void)hipMemsetAsync(c.kc0 + (size_t)s * c.kv_seq_elems, 0, c.kv_seq_elems * 2, c.stream);
     (void)hipMemsetAsync(c.vc0 + (size_t)s * c.kv_seq_elems, 0, c.kv_seq_elems * 2, c.stream);
     (void)hipMemsetAsync(c.hist0 + (size_t)s * c.n_ctx, 0, (size_t)c.n_ctx * 4, c.stream);
-    StepState s0{};
-    s0.token_in = -1;
-    s0.token_in_pos = -1;
+    const StepState s0 = fresh_step_state();
     (void)hipMemcpyAsync(c.st0 + s, &s0, sizeof s0, hipMemcpyHostToDevice, c.stream);
     (void)hipStreamSynchronize(c.stream);
     if (s < (int)c.seq_past.size()) c.seq_past[(size_t)s] = 0;
@@ -482,20 +514,12 @@ void context_clear(Context& c) {
     (void)hipMemsetAsync(c.kc0, 0, kv_elems * 2, c.stream);
     (void)hipMemsetAsync(c.vc0, 0, kv_elems * 2, c.stream);
     (void)hipMemsetAsync(c.hist0, 0, (size_t)c.n_ctx * 4 * nalloc, c.stream);
-    for (int s = 1; s < nalloc; ++s) {
-        StepState s1{};
-        s1.token_in = -1;
-        s1.token_in_pos = -1;
-        (void)hipMemcpyAsync(c.st0 + s, &s1, sizeof s1, hipMemcpyHostToDevice, c.stream);
-    }
+    const StepState s0 = fresh_step_state();
+    for (int s = 0; s < nalloc; ++s) (void)hipMemcpyAsync(c.st0 + s, &s0, sizeof s0, hipMemcpyHostToDevice, c.stream);
     std::fill(c.seq_past.begin(), c.seq_past.end(), 0);
     // attention scratch incl. k_attn_x's granules: the step sequence restarts at 0 below,
     // so no granule of an earlier sequence may keep a tag the new one will use
     (void)hipMemsetAsync(c.scores, 0, attn_scratch_floats(hp.n_head, c.n_ctx) * 4, c.stream);
-    StepState s0{};
-    s0.token_in = -1;
-    s0.token_in_pos = -1;
-    (void)hipMemcpyAsync(c.st0, &s0, sizeof s0, hipMemcpyHostToDevice, c.stream);
     (void)hipStreamSynchronize(c.stream);
     c.n_past = 0;
 }
@@ -558,9 +582,6 @@ Seg seg_of(const Model& m, const DevMat& d, int row0) {
     s.x86 = m.numerics == NUMERICS_X86;
     return s;
 }
-
-namespace {
-}  // namespace
 
 #if defined(LLMI_EXPERIMENTS)
 // LLMI_EXP_XQ (step_enqueue): a zero q8 image, allocated before any capture
@@ -671,12 +692,10 @@ bool step_enqueue(Context& c, int kv_bound, std::string& err) {
         qkv_done = false;
         // --- attention ---
         AttnArgs at;
-        at.q = c.q; at.kc = c.kc + l * kv_layer; at.vc = c.vc + l * kv_layer; at.scores = c.scores; at.out = c.att; at.st = c.st;
-        at.tmax = c.scores + (size_t)hp.n_head * c.n_ctx;
+        at.q = c.q; at.kc = c.kc + l * kv_layer; at.vc = c.vc + l * kv_layer; at.out = c.att; at.st = c.st;
+        attn_bind_scratch(at, c.scores, hp.n_head, c.n_ctx);  // at.fault = c.fault_dev
         at.n_ctx = c.n_ctx; at.scale = 1.0f / sqrtf((float)D);
         at.layer = l;
-        at.gran = (unsigned long long*)(c.scores + attn_gran_off(hp.n_head, c.n_ctx));
-        at.fault = c.fault_dev;
         at.num = num;
         at.fa = m.fa;
         LLMI_RUN(K_ATTN, launch_attention(at, hp.n_head, hp.n_head_kv, D, kv_bound, c.stream));
@@ -744,23 +763,14 @@ bool step_run(Context& c, int pos, std::string& err) {
 #if defined(LLMI_EXPERIMENTS)
     if (!exp_prepare(*c.m)) { err = "exp_img"; return false; }
 #endif
-    const int bucket = pos / 256;
-    const int kv_bound = std::min(c.n_ctx, (bucket + 1) * 256);
+    const int kv_bound = kv_bucket_bound(pos + 1, c.n_ctx);
     if (!c.use_graphs) return step_enqueue(c, kv_bound, err);
+    const int bucket = pos / 256;
     const int gkey = bucket * 256 + c.cur_seq;
     auto it = c.graphs.find(gkey);
     if (it == c.graphs.end()) {
-        hipGraph_t g = nullptr;
-        HIPC(hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal));
-        std::string e2;
-        const bool ok = step_enqueue(c, kv_bound, e2);
-        hipError_t ec = hipStreamEndCapture(c.stream, &g);
-        if (!ok) { err = "capture: " + e2; if (g) (void)hipGraphDestroy(g); return false; }
-        if (ec != hipSuccess) { err = "hipStreamEndCapture: " + hip_err(ec); return false; }
-        hipGraphExec_t ex = nullptr;
-        hipError_t ei = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (ei != hipSuccess) { err = "hipGraphInstantiate: " + hip_err(ei); return false; }
+        hipGraphExec_t ex = capture_graph(c.stream, [&](std::string& e) { return step_enqueue(c, kv_bound, e); }, err);
+        if (!ex) return false;
         it = c.graphs.emplace(gkey, ex).first;
     }
     HIPC(hipGraphLaunch(it->second, c.stream));
@@ -869,7 +879,7 @@ static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std
             AttnArgs& at = ba.a[s];
             const size_t sq = (size_t)seqs[s] * c.kv_seq_elems;
             at.q = c.bq + (size_t)s * QD; at.kc = c.kc0 + sq + l * kv_layer; at.vc = c.vc0 + sq + l * kv_layer;
-            at.scores = c.bscores + (size_t)s * scr; at.tmax = at.scores + (size_t)hp.n_head * c.n_ctx;
+            attn_bind_scratch(at, c.bscores + (size_t)s * scr, hp.n_head, c.n_ctx, false);
             at.out = c.batt + (size_t)s * QD; at.st = c.st0 + seqs[s]; at.n_ctx = c.n_ctx;
             at.scale = 1.0f / sqrtf((float)D); at.layer = l;
             at.num = m.numerics;
@@ -911,7 +921,7 @@ bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& er
         if (L.wg.type != L.wu.type) { err = "batched step: ffn_gate / ffn_up of different types"; return false; }
     if (!balloc(c, err)) return false;
     const int bucket = max_pos / 256;
-    const int kv_bound = std::min(c.n_ctx, (bucket + 1) * 256);
+    const int kv_bound = kv_bucket_bound(max_pos + 1, c.n_ctx);
     if (hp.n_head / hp.n_head_kv > 8 && (size_t)(hp.n_head / hp.n_head_kv) * kv_bound * 4 > kSplitAttnMaxLds) {
         err = "batched step: context too long for GQA groups of more than 8 heads";
         return false;
@@ -929,17 +939,9 @@ bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& er
     for (int s = 0; s < nt; ++s) key += "," + std::to_string(seqs[s]);
     auto it = c.bgraphs.find(key);
     if (it == c.bgraphs.end()) {
-        hipGraph_t g = nullptr;
-        HIPC(hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal));
-        std::string e2;
-        const bool ok = bstep_enqueue(c, nt, seqs, kv_bound, e2);
-        hipError_t ec = hipStreamEndCapture(c.stream, &g);
-        if (!ok) { err = "capture: " + e2; if (g) (void)hipGraphDestroy(g); return false; }
-        if (ec != hipSuccess) { err = "hipStreamEndCapture: " + hip_err(ec); return false; }
-        hipGraphExec_t ex = nullptr;
-        hipError_t ei = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (ei != hipSuccess) { err = "hipGraphInstantiate: " + hip_err(ei); return false; }
+        hipGraphExec_t ex =
+            capture_graph(c.stream, [&](std::string& e) { return bstep_enqueue(c, nt, seqs, kv_bound, e); }, err);
+        if (!ex) return false;
         it = c.bgraphs.emplace(key, ex).first;
     }
     HIPC(hipGraphLaunch(it->second, c.stream));
@@ -1031,7 +1033,7 @@ bool prefill_enqueue(Context& c, const int32_t* tokens, int n, int pos0, std::st
     if (!prefill_supported(m)) { err = "prefill: model shapes not supported by the batched path"; return false; }
     if (pos0 < 0 || pos0 + n > c.n_ctx) { err = "prefill: positions out of the context"; return false; }
     if (!prefill_alloc(c, err)) return false;
-    const int E = hp.n_embd, D = hp.head_dim, nq = hp.n_head * D, nk = hp.n_head_kv * D, F = hp.n_ff;
+    const int E = hp.n_embd, D = hp.head_dim, nq = hp.n_head * D, F = hp.n_ff;
     const size_t kv_layer = (size_t)hp.n_head_kv * c.n_ctx * D;
     const int x86 = m.numerics == NUMERICS_X86;
 #define PFC(expr)                                                              \
@@ -1049,36 +1051,18 @@ bool prefill_enqueue(Context& c, const int32_t* tokens, int n, int pos0, std::st
             g.T = T; g.aq = c.pf_aq; g.abs = c.pf_abs; g.ad = c.pf_ad; g.abf = c.pf_abf;
             g.kc = c.kc + l * kv_layer; g.vc = c.vc + l * kv_layer; g.rope = c.rope;
             g.pos0 = p0; g.head_dim = D; g.n_rot = hp.n_rot; g.n_ctx = c.n_ctx;
-            // q, k, v (each quantized for its own activation kind)
-            const DevMat* qkv[3] = {&L.wq, &L.wk, &L.wv};
-            int quant_kind = -1;
-            // consecutive same-type parts (rows multiples of 64) share one launch
-            for (int part = 0; part < 3;) {
-                const DevMat& W = *qkv[part];
-                if (act_kind(W.type) != quant_kind) {
-                    quant_kind = act_kind(W.type);
-                    PFC(launch_pf_quant(c.pf_x, E, (const float*)(m.arena + L.attn_norm.off_a), hp.eps, E, quant_kind, T,
+            // q, k, v (each quantized for its own activation kind; pf_qkv_launches)
+            g.cols = E; g.y = c.pf_q; g.ldy = nq;
+            const Seg qkv[3] = {seg_of(m, L.wq, 0), seg_of(m, L.wk, 0), seg_of(m, L.wv, 0)};
+            PfGemm qg[3];
+            int qkind[3];
+            const int nqg = pf_qkv_launches(qkv, g_pf_qkv_merge != 0, g, qg, qkind);
+            for (int i = 0; i < nqg; ++i) {
+                if (qkind[i] >= 0)
+                    PFC(launch_pf_quant(c.pf_x, E, (const float*)(m.arena + L.attn_norm.off_a), hp.eps, E, qkind[i], T,
                                         c.pf_aq, c.pf_abs, c.pf_ad, c.pf_abf, c.stream, x86));
-                }
-                int end = part + 1;
-                while (g_pf_qkv_merge && end < 3 && qkv[end]->type == W.type && qkv[end - 1]->rows % 64 == 0) ++end;
-                g.w = seg_of(m, W, 0); g.rows = (int)W.rows; g.cols = E; g.part = part; g.r1 = g.r2 = 0;
-                if (end > part + 1) {
-                    g.wk = seg_of(m, *qkv[part + 1], 0);
-                    g.r1 = (int)W.rows;
-                    g.r2 = g.r1 + (int)qkv[part + 1]->rows;
-                    g.rows = g.r2;
-                    if (end > part + 2) {
-                        g.wv = seg_of(m, *qkv[part + 2], 0);
-                        g.rows += (int)qkv[part + 2]->rows;
-                    }
-                }
-                g.y = c.pf_q; g.ldy = nq;
-                PFC(launch_pf_gemm(g, EPI_QKV, c.stream));
-                part = end;
+                PFC(launch_pf_gemm(qg[i], EPI_QKV, c.stream));
             }
-            g.r1 = g.r2 = 0;
-            (void)nk;
             PfAttn at;
             at.q = c.pf_q; at.out = c.pf_att; at.ldq = nq; at.kc = g.kc; at.vc = g.vc;
             at.n_ctx = c.n_ctx; at.pos0 = p0; at.gqa = hp.n_head / hp.n_head_kv; at.max_kv = p0 + T;

@@ -198,5 +198,10 @@ std::string hip_err(hipError_t e);
 // matvec grid cap = CUs x wg_per_cu() workgroups (env LLMI_WG_PER_CU, read when a context
 // is created; default 2: measured best on every config, profiles/r01/wg_sweep.md)
 int wg_per_cu();
+int mv_grid_cap(int device);  // at least 64; 0: the device query failed
+// Captures what `enqueue` puts on `s` (thread-local capture mode) into an executable
+// graph.  Null and err set when capture, enqueue ("capture: " + its error) or
+// instantiation fails; the captured graph itself is destroyed on every way out.
+hipGraphExec_t capture_graph(hipStream_t s, const std::function<bool(std::string&)>& enqueue, std::string& err);
 
 }  // namespace llmi

@@ -21,7 +21,7 @@ constexpr int kXAttnMaxKV = 1024;    // one-launch exchange attention (k_attn_x)
 constexpr int kDimAttnMaxKV = 1024;  // dim-split one-launch attention (k_attn_d) up to this KV bound
 constexpr int kRegAttnMaxKV = 512;   // register-prefetched one-launch attention (k_attn_r) up to this KV bound
 constexpr int kPfAttnMaxKV = 32768;  // batched-prefill attention: scores of one head in LDS
-// test options (llmi_test_option in capi.cpp): bit-identical path selection and lowered limits
+// test options (llmi_test_option in capi_hooks.cpp): bit-identical path selection and lowered limits
 extern int g_mv_unit_split, g_mv_split_nt;  // matvec unit split (kernels.hip LLMI_MV_SPLIT: -1 auto, 0 .. 3) and the workgroup threads of split launches (0 auto, 256, 512)
 extern int g_pf_fa_noalloc, g_pf_gemm_ng, g_pf_qkv_merge, g_pf_xcd_map, g_pf_quant_bpc, g_pf_quant_split_below, g_pf_attn_simple, g_pf_attn_fa, g_pf_fa_cfg, g_pf_max_kv, g_xspin_limit, g_xtag_skew;
 int pf_max_kv();  // llama_decode hands prompt runs reaching past this KV length to decode steps
@@ -33,7 +33,8 @@ __host__ __device__ inline size_t attn_gran_off(int n_head, int n_ctx) {
 // + the long-context path's (k_attl_*) per-256-position tile sums [H][n_ctx/256] and PV
 // partials [H][n_ctx/256][<= 128 dims], both double
 constexpr int kLongTile = 256;
-__host__ __device__ inline size_t attn_long_off(int n_head, int n_ctx) { return attn_gran_off(n_head, n_ctx) + 2 * (size_t)n_head * kXAttnMaxKV + 4; }
+__host__ __device__ inline size_t attn_fault_off(int n_head, int n_ctx) { return attn_gran_off(n_head, n_ctx) + 2 * (size_t)n_head * kXAttnMaxKV; }
+__host__ __device__ inline size_t attn_long_off(int n_head, int n_ctx) { return attn_fault_off(n_head, n_ctx) + 4; }
 inline size_t attn_scratch_floats(int n_head, int n_ctx) {
     return attn_long_off(n_head, n_ctx) + 2 * (size_t)n_head * ((n_ctx + kLongTile - 1) / kLongTile) * 129;
 }
@@ -281,6 +282,52 @@ inline int qkv_launch_groups(const Seg (&qkv)[3], bool by_act, const MVArgs& bas
         i = j;
     }
     return n;
+}
+
+// The q / k / v launches of a prefill layer: consecutive parts of one weight type share a
+// launch when the earlier part's rows are a multiple of 64 (merge: the pf_qkv_merge test
+// option).  out[i] = base with w / wk / wv, rows, r1, r2 and part of launch i; quant[i] = the
+// activation kind to quantize before it, -1: it reads the previous launch's image.  Returns
+// the number of launches.  (prefill_enqueue and the llmi_mv_epilogue hook share it.)
+inline int pf_qkv_launches(const Seg (&qkv)[3], bool merge, const PfGemm& base, PfGemm (&out)[3], int (&quant)[3]) {
+    int n = 0, kind = -1;
+    for (int part = 0; part < 3;) {
+        int end = part + 1;
+        while (merge && end < 3 && qkv[end].type == qkv[part].type && qkv[end - 1].rows % 64 == 0) ++end;
+        PfGemm g = base;
+        Seg* w[3] = {&g.w, &g.wk, &g.wv};
+        g.part = part;
+        g.rows = 0;
+        for (int k = part; k < end; ++k) {
+            *w[k - part] = qkv[k];
+            w[k - part]->row0 = 0;  // every part's rows are its own matrix's
+            g.rows += qkv[k].rows;
+        }
+        g.r1 = end > part + 1 ? qkv[part].rows : 0;
+        g.r2 = end > part + 1 ? g.r1 + qkv[part + 1].rows : 0;
+        quant[n] = act_kind(qkv[part].type) != kind ? (kind = act_kind(qkv[part].type)) : -1;
+        out[n++] = g;
+        part = end;
+    }
+    return n;
+}
+
+// KV bound of a launch that reads n_kv positions: the end of their 256-position bucket, at
+// most the context.  (A step at position pos passes pos + 1: (pos / 256 + 1) * 256 and
+// (pos + 1 + 255) / 256 * 256 are equal for pos >= 0.)
+inline int kv_bucket_bound(int n_kv, int n_ctx) {
+    const int b = (n_kv + 255) / 256 * 256;
+    return b < n_ctx ? b : n_ctx;
+}
+
+// Points a's scores, tmax, gran and fault at their places in one attention scratch of
+// attn_scratch_floats(n_head, n_ctx) floats.  exchange = false leaves gran and fault null
+// (the batched step: none of its paths reads them).
+inline void attn_bind_scratch(AttnArgs& a, float* base, int n_head, int n_ctx, bool exchange = true) {
+    a.scores = base;
+    a.tmax = base + (size_t)n_head * n_ctx;
+    a.gran = exchange ? (unsigned long long*)(base + attn_gran_off(n_head, n_ctx)) : nullptr;
+    a.fault = exchange ? (unsigned*)(base + attn_fault_off(n_head, n_ctx)) : nullptr;
 }
 
 // All launches are asynchronous on `stream` and graph-capturable (no allocation, no sync).

@@ -1109,8 +1109,8 @@ __device__ __forceinline__ void store_terms(float* F, int r, int ul, int lr, con
     }
 }
 
-// (the descriptor type is a template parameter: the persistent step reads its phase
-// descriptors through the constant address space, step.hip)
+// (the descriptor type is a template parameter: the layer engine, leng.hip, hands its
+// ops' descriptors to the same code)
 template <class MA>
 __device__ __forceinline__ Seg pick(const MA& A, int si) {
     Seg s;
@@ -1168,8 +1168,8 @@ __device__ __forceinline__ unsigned long long argmax_key(float v, int row) {
     return ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (uint32_t)row);
 }
 
-// Global accesses of data handed between the phases of ONE launch (the persistent step,
-// step.hip): write-through `sc1` stores and `sc1` loads (relaxed agent-scope atomics),
+// Global accesses of data handed between the ops of ONE launch (the layer engine,
+// leng.hip, the user of WT = true): write-through `sc1` stores and `sc1` loads (relaxed agent-scope atomics),
 // the hand-off form MI355X_MICROARCH.md §visibility validates without acquire fences.
 // WT = false: plain accesses (separate launches hand over at kernel boundaries).
 typedef unsigned int __attribute__((address_space(1))) gu32_t;
