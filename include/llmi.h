@@ -188,6 +188,30 @@ int32_t llmi_generate_greedy(struct llama_context* ctx, llama_token first, int32
  * that sequence alone (n = 1 runs the single-sequence step).  Returns n_gen or < 0 on error. */
 int32_t llmi_generate_greedy_batch(struct llama_context* ctx, int32_t n, const int32_t* seqs, const llama_token* first,
                                    const int32_t* pos0, int32_t n_gen, llama_token* out);
+/* One sequence's sampler chain (llama-server's: penalties -> top_k -> top_p -> min_p ->
+ * temperature -> dist, llmi/sampling.py).  The fields are doubles because the host
+ * definition computes with Python floats.  The device path takes 1 <= top_k <=
+ * LLMI_SAMPLE_MAX_TOP_K and 0 <= repeat_last_n <= LLMI_SAMPLE_MAX_LAST_N (the penalty window:
+ * the last repeat_last_n tokens up to and including the step's input token). */
+#define LLMI_SAMPLE_MAX_TOP_K 256
+#define LLMI_SAMPLE_MAX_LAST_N 256
+struct llmi_sampler_params {
+    double temperature, top_p, min_p, repeat_penalty, presence_penalty, frequency_penalty;
+    int32_t top_k, repeat_last_n;
+};
+/* llmi_generate_greedy_batch with the sampler chain run on the device after every step's
+ * logits (k_sample), the chosen token fed back as the argmax is: no logits leave the device.
+ * params[k] is sequence k's chain; a chain that is an argmax of the raw logits (temperature
+ * <= 0 or top_k == 1, no penalties) makes that sequence greedy, bit-identical to
+ * llmi_generate_greedy_batch, so one call serves any mix.  uniforms[k * n_gen + j] in [0, 1)
+ * is the draw of sequence k's step j (numpy's Generator.choice: the first candidate whose
+ * cumulative probability exceeds it); out[k * n_gen + j] equals llmi/sampling.py's
+ * sample_with_uniform on that step's logits.  Arguments, return codes, bounded waits and
+ * fault read-back as llmi_generate_greedy_batch; parameters outside the device limits (or not
+ * finite) are refused with -1 before any device work, the error naming the field. */
+int32_t llmi_generate_sampled_batch(struct llama_context* ctx, int32_t n, const int32_t* seqs, const llama_token* first,
+                                    const int32_t* pos0, int32_t n_gen, const struct llmi_sampler_params* params,
+                                    const double* uniforms, llama_token* out);
 /* seconds the weight upload took in llama_model_load_from_file (chunked pinned H2D,
  * double-buffered against the on-device repack; file reads included) */
 double llmi_model_upload_s(const struct llama_model* model);
@@ -500,6 +524,18 @@ double llmi_bench_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim,
  * Returns the requested grid size, < 0 on error. */
 int32_t llmi_trace_matvec(int32_t type, const void* w_dev, int64_t rows, int64_t cols, const float* x_dev, float* y_dev,
                           int32_t mode, uint64_t* trace_dev);
+/* k_sample alone (what a sampled step launches after its logits), no model.  All pointers
+ * are HOST memory: logits [n_rows][V] f32 rows (1 <= n_rows <= 8), hist [n_rows][n_hist]
+ * each row's token history (the step's position is n_hist - 1; n_hist 0: none, hist may be
+ * NULL), params [n_rows], uniforms [n_rows].  Out: token_out [n_rows] the chosen token (a
+ * greedy row: the argmax of its logits), cand_out [n_rows][LLMI_SAMPLE_MAX_TOP_K] the final
+ * candidate ids in order, n_cand_out [n_rows] their number (0 for a greedy row),
+ * penalized_out [n_rows][n_hist] the row's values at its history tokens after the kernel (0
+ * for an id outside [0, V); NULL: not wanted), us_out (optional) the launch's event-timed
+ * microseconds.  Arguments are checked before any device call.  Returns 0 or < 0. */
+int32_t llmi_sample_logits(const float* logits, int32_t n_rows, int32_t V, const int32_t* hist, int32_t n_hist,
+                           const struct llmi_sampler_params* params, const double* uniforms, int32_t* token_out,
+                           int32_t* cand_out, int32_t* n_cand_out, float* penalized_out, double* us_out);
 
 #pragma GCC visibility pop
 

@@ -36,6 +36,134 @@ bool ensure_outs(llama_context* ctx, int n) {
     }
     return true;
 }
+
+int seq_past_of(const Context& c, int s) { return s == c.cur_seq ? c.n_past : c.seq_past[(size_t)s]; }
+void set_seq_past(Context& c, int s, int v) {
+    if (s == c.cur_seq) c.n_past = v;
+    else c.seq_past[(size_t)s] = v;
+}
+
+// llmi_generate_greedy's body; sampled: the steps end with k_sample (the caller has uploaded
+// the records and uniforms, sample_prepare)
+int32_t generate_one(const char* name, llama_context* ctx, llama_token first, int32_t pos0, int32_t n_gen, llama_token* out,
+                     bool sampled) {
+    const std::string who = std::string(name) + ": ";
+    if (!ctx || !out || n_gen <= 0) { set_err(who + "bad arguments"); return -1; }
+    Context& c = ctx->c;
+    const HParams& hp = c.m->hp;
+    if (first < 0 || first >= hp.n_vocab) { set_err(who + "token out of range"); return -1; }
+    if (pos0 < 0 || pos0 + n_gen > c.n_ctx) { set_err(who + "exceeds n_ctx"); return 1; }
+    (void)hipSetDevice(c.m->device);
+    (void)hipGetLastError();
+    std::string err;
+    double bytes = 0;
+    if (launch_state_set(c.st, first, pos0, c.stream) != hipSuccess) { set_err("state set failed"); return -3; }
+    hipEventRecord(c.ev0, c.stream);
+    for (int k = 0; k < n_gen; ++k) {
+        if (!step_run(c, pos0 + k, err, sampled)) {
+            if (sampled) (void)hipStreamSynchronize(c.stream);  // sample_prepare's copies read the context's host vectors
+            set_err(who + err);
+            return -3;
+        }
+        bytes += bytes_per_token(*c.m, pos0 + k + 1);
+    }
+    hipEventRecord(c.ev1, c.stream);
+    std::vector<int32_t> h((size_t)n_gen);
+    unsigned long long keys[kArgSlots];
+    if (n_gen > 1)
+        (void)hipMemcpyAsync(h.data(), c.hist + pos0 + 1, (size_t)(n_gen - 1) * 4, hipMemcpyDeviceToHost, c.stream);
+    (void)hipMemcpyAsync(keys, &c.st->key[(pos0 + n_gen - 1) & 1][0], sizeof(keys), hipMemcpyDeviceToHost, c.stream);
+    context_fault_readback(c);
+    hipError_t e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) { set_err(who + hip_err(e)); return -4; }
+    if (!context_fault_ok(c, err)) { set_err(who + err); return -6; }
+    for (int k = 0; k + 1 < n_gen; ++k) out[k] = h[(size_t)k];
+    out[n_gen - 1] = (llama_token)key_token(keys);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, c.ev0, c.ev1);
+    c.last_us = ms * 1e3;
+    c.last_bytes = bytes;
+    c.n_past = pos0 + n_gen;
+    c.n_outputs = 0;
+    return n_gen;
+}
+
+// llmi_generate_greedy_batch's body; recs (n records) and uniforms (n x n_gen) non-null: the
+// sampled call, every step ending with k_sample
+int32_t generate_batch(const char* name, llama_context* ctx, int32_t n, const int32_t* seqs, const llama_token* first,
+                       const int32_t* pos0, int32_t n_gen, llama_token* out, const SampleRec* recs, const double* uniforms) {
+    const std::string who = std::string(name) + ": ";
+    const bool sampled = recs != nullptr;
+    if (!ctx || n <= 0 || n > kMaxBatch || !seqs || !first || !pos0 || !out || n_gen <= 0) {
+        set_err(who + "bad arguments (1..8 sequences)");
+        return -1;
+    }
+    Context& c = ctx->c;
+    const HParams& hp = c.m->hp;
+    for (int k = 0; k < n; ++k) {
+        if (seqs[k] < 0 || seqs[k] >= c.n_seq) { set_err(who + "seq out of range (n_seq_max)"); return -1; }
+        for (int j = 0; j < k; ++j)
+            if (seqs[j] == seqs[k]) { set_err(who + "repeated sequence"); return -1; }
+        if (first[k] < 0 || first[k] >= hp.n_vocab) { set_err(who + "token out of range"); return -1; }
+        if (pos0[k] < 0 || pos0[k] + n_gen > c.n_ctx) { set_err(who + "exceeds n_ctx"); return 1; }
+    }
+    (void)hipSetDevice(c.m->device);
+    (void)hipGetLastError();
+    std::string err;
+    if (sampled && !sample_prepare(c, n, recs, pos0, uniforms, n_gen, err)) { set_err(who + err); return -3; }
+    if (n == 1) {  // one sequence: the single-sequence step (k_matvec path, its own graphs)
+        context_select_seq(c, seqs[0]);
+        return generate_one(name, ctx, first[0], pos0[0], n_gen, out, sampled);
+    }
+    double bytes = 0;
+    for (int k = 0; k < n; ++k)
+        if (launch_state_set(c.st0 + seqs[k], first[k], pos0[k], c.stream) != hipSuccess) {
+            if (sampled) (void)hipStreamSynchronize(c.stream);
+            set_err("state set failed");
+            return -3;
+        }
+    hipEventRecord(c.ev0, c.stream);
+    for (int j = 0; j < n_gen; ++j) {
+        int max_pos = 0;
+        for (int k = 0; k < n; ++k) {
+            max_pos = std::max(max_pos, pos0[k] + j);
+            bytes += bytes_per_token(*c.m, pos0[k] + j + 1) / n;
+        }
+        if (!bstep_run(c, n, seqs, max_pos, err, sampled)) {
+            // (a model without a batched step ends here; the caller may call again at once, and
+            // sample_prepare's pending copies still read the context's host vectors)
+            if (sampled) (void)hipStreamSynchronize(c.stream);
+            set_err(who + err);
+            return -3;
+        }
+    }
+    hipEventRecord(c.ev1, c.stream);
+    std::vector<int32_t> h((size_t)n * n_gen);
+    std::vector<unsigned long long> keys((size_t)n * kArgSlots);
+    for (int k = 0; k < n; ++k) {
+        const int32_t* hist = c.hist0 + (size_t)seqs[k] * c.n_ctx;
+        if (n_gen > 1)
+            (void)hipMemcpyAsync(h.data() + (size_t)k * n_gen, hist + pos0[k] + 1, (size_t)(n_gen - 1) * 4, hipMemcpyDeviceToHost,
+                                 c.stream);
+        (void)hipMemcpyAsync(keys.data() + (size_t)k * kArgSlots, &c.st0[seqs[k]].key[(pos0[k] + n_gen - 1) & 1][0],
+                             8 * kArgSlots, hipMemcpyDeviceToHost, c.stream);
+    }
+    context_fault_readback(c);
+    hipError_t e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) { set_err(who + hip_err(e)); return -4; }
+    if (!context_fault_ok(c, err)) { set_err(who + err); return -6; }
+    for (int k = 0; k < n; ++k) {
+        for (int j = 0; j + 1 < n_gen; ++j) out[(size_t)k * n_gen + j] = h[(size_t)k * n_gen + j];
+        out[(size_t)k * n_gen + n_gen - 1] = (llama_token)key_token(keys.data() + (size_t)k * kArgSlots);
+        set_seq_past(c, seqs[k], pos0[k] + n_gen);
+    }
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, c.ev0, c.ev1);
+    c.last_us = ms * 1e3;
+    c.last_bytes = bytes;
+    c.n_outputs = 0;
+    return n_gen;
+}
 }  // namespace
 
 extern "C" {
@@ -158,12 +286,6 @@ void llama_batch_free(struct llama_batch b) {
 
 // shortest prompt run taken by the batched prefill path (shorter runs: decode steps)
 static constexpr int kPrefillMin = 2;
-
-static int seq_past_of(const Context& c, int s) { return s == c.cur_seq ? c.n_past : c.seq_past[(size_t)s]; }
-static void set_seq_past(Context& c, int s, int v) {
-    if (s == c.cur_seq) c.n_past = v;
-    else c.seq_past[(size_t)s] = v;
-}
 
 static void copy_out(llama_context* ctx, int r, const float* logits_dev, const StepState* st, int pos) {
     Context& c = ctx->c;
@@ -371,107 +493,42 @@ llama_token llmi_greedy_ith(struct llama_context* ctx, int32_t i) {
 
 int32_t llmi_generate_greedy(struct llama_context* ctx, llama_token first, int32_t pos0, int32_t n_gen, llama_token* out) {
     API_TRY
-    if (!ctx || !out || n_gen <= 0) { set_err("llmi_generate_greedy: bad arguments"); return -1; }
-    Context& c = ctx->c;
-    const HParams& hp = c.m->hp;
-    if (first < 0 || first >= hp.n_vocab) { set_err("llmi_generate_greedy: token out of range"); return -1; }
-    if (pos0 < 0 || pos0 + n_gen > c.n_ctx) { set_err("llmi_generate_greedy: exceeds n_ctx"); return 1; }
-    (void)hipSetDevice(c.m->device);
-    (void)hipGetLastError();
-    std::string err;
-    double bytes = 0;
-    if (launch_state_set(c.st, first, pos0, c.stream) != hipSuccess) { set_err("state set failed"); return -3; }
-    hipEventRecord(c.ev0, c.stream);
-    for (int k = 0; k < n_gen; ++k) {
-        if (!step_run(c, pos0 + k, err)) { set_err("llmi_generate_greedy: " + err); return -3; }
-        bytes += bytes_per_token(*c.m, pos0 + k + 1);
-    }
-    hipEventRecord(c.ev1, c.stream);
-    std::vector<int32_t> h((size_t)n_gen);
-    unsigned long long keys[kArgSlots];
-    if (n_gen > 1)
-        (void)hipMemcpyAsync(h.data(), c.hist + pos0 + 1, (size_t)(n_gen - 1) * 4, hipMemcpyDeviceToHost, c.stream);
-    (void)hipMemcpyAsync(keys, &c.st->key[(pos0 + n_gen - 1) & 1][0], sizeof(keys), hipMemcpyDeviceToHost, c.stream);
-    context_fault_readback(c);
-    hipError_t e = hipStreamSynchronize(c.stream);
-    if (e != hipSuccess) { set_err("llmi_generate_greedy: " + hip_err(e)); return -4; }
-    if (!context_fault_ok(c, err)) { set_err("llmi_generate_greedy: " + err); return -6; }
-    for (int k = 0; k + 1 < n_gen; ++k) out[k] = h[(size_t)k];
-    out[n_gen - 1] = (llama_token)key_token(keys);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, c.ev0, c.ev1);
-    c.last_us = ms * 1e3;
-    c.last_bytes = bytes;
-    c.n_past = pos0 + n_gen;
-    c.n_outputs = 0;
-    return n_gen;
+    return generate_one("llmi_generate_greedy", ctx, first, pos0, n_gen, out, false);
     API_CATCH(-5)
 }
 
 int32_t llmi_generate_greedy_batch(struct llama_context* ctx, int32_t n, const int32_t* seqs, const llama_token* first,
                                    const int32_t* pos0, int32_t n_gen, llama_token* out) {
     API_TRY
-    if (!ctx || n <= 0 || n > kMaxBatch || !seqs || !first || !pos0 || !out || n_gen <= 0) {
-        set_err("llmi_generate_greedy_batch: bad arguments (1..8 sequences)");
+    return generate_batch("llmi_generate_greedy_batch", ctx, n, seqs, first, pos0, n_gen, out, nullptr, nullptr);
+    API_CATCH(-5)
+}
+
+int32_t llmi_generate_sampled_batch(struct llama_context* ctx, int32_t n, const int32_t* seqs, const llama_token* first,
+                                    const int32_t* pos0, int32_t n_gen, const struct llmi_sampler_params* params,
+                                    const double* uniforms, llama_token* out) {
+    API_TRY
+    const char* name = "llmi_generate_sampled_batch";
+    // what needs no context first: refusals name their field before any device work
+    if (n <= 0 || n > kMaxBatch || !seqs || !first || !pos0 || !out || n_gen <= 0 || !params || !uniforms) {
+        set_err(std::string(name) + ": bad arguments (1..8 sequences, no null pointers)");
         return -1;
     }
-    Context& c = ctx->c;
-    const HParams& hp = c.m->hp;
-    int max_end = 0;
-    for (int k = 0; k < n; ++k) {
-        if (seqs[k] < 0 || seqs[k] >= c.n_seq) { set_err("llmi_generate_greedy_batch: seq out of range (n_seq_max)"); return -1; }
-        for (int j = 0; j < k; ++j)
-            if (seqs[j] == seqs[k]) { set_err("llmi_generate_greedy_batch: repeated sequence"); return -1; }
-        if (first[k] < 0 || first[k] >= hp.n_vocab) { set_err("llmi_generate_greedy_batch: token out of range"); return -1; }
-        if (pos0[k] < 0 || pos0[k] + n_gen > c.n_ctx) { set_err("llmi_generate_greedy_batch: exceeds n_ctx"); return 1; }
-        max_end = std::max(max_end, pos0[k] + n_gen);
-    }
-    if (n == 1) {  // one sequence: the single-sequence step (k_matvec path, its own graphs)
-        context_select_seq(c, seqs[0]);
-        return llmi_generate_greedy(ctx, first[0], pos0[0], n_gen, out);
-    }
-    (void)hipSetDevice(c.m->device);
-    (void)hipGetLastError();
-    std::string err;
-    double bytes = 0;
     for (int k = 0; k < n; ++k)
-        if (launch_state_set(c.st0 + seqs[k], first[k], pos0[k], c.stream) != hipSuccess) { set_err("state set failed"); return -3; }
-    hipEventRecord(c.ev0, c.stream);
-    for (int j = 0; j < n_gen; ++j) {
-        int max_pos = 0;
-        for (int k = 0; k < n; ++k) {
-            max_pos = std::max(max_pos, pos0[k] + j);
-            bytes += bytes_per_token(*c.m, pos0[k] + j + 1) / n;
+        for (int j = 0; j < k; ++j)
+            if (seqs[j] == seqs[k]) { set_err(std::string(name) + ": repeated sequence"); return -1; }
+    std::vector<SampleRec> recs((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const llmi_sampler_params& p = params[k];
+        std::string why;
+        if (!sample_rec_make(p.temperature, p.top_k, p.top_p, p.min_p, p.repeat_penalty, p.repeat_last_n, p.presence_penalty,
+                             p.frequency_penalty, recs[(size_t)k], why)) {
+            set_err(std::string(name) + ": params[" + std::to_string(k) + "]: " + why + " (the device sampler's limits)");
+            return -1;
         }
-        if (!bstep_run(c, n, seqs, max_pos, err)) { set_err("llmi_generate_greedy_batch: " + err); return -3; }
     }
-    hipEventRecord(c.ev1, c.stream);
-    std::vector<int32_t> h((size_t)n * n_gen);
-    std::vector<unsigned long long> keys((size_t)n * kArgSlots);
-    for (int k = 0; k < n; ++k) {
-        const int32_t* hist = c.hist0 + (size_t)seqs[k] * c.n_ctx;
-        if (n_gen > 1)
-            (void)hipMemcpyAsync(h.data() + (size_t)k * n_gen, hist + pos0[k] + 1, (size_t)(n_gen - 1) * 4, hipMemcpyDeviceToHost,
-                                 c.stream);
-        (void)hipMemcpyAsync(keys.data() + (size_t)k * kArgSlots, &c.st0[seqs[k]].key[(pos0[k] + n_gen - 1) & 1][0],
-                             8 * kArgSlots, hipMemcpyDeviceToHost, c.stream);
-    }
-    context_fault_readback(c);
-    hipError_t e = hipStreamSynchronize(c.stream);
-    if (e != hipSuccess) { set_err("llmi_generate_greedy_batch: " + hip_err(e)); return -4; }
-    if (!context_fault_ok(c, err)) { set_err("llmi_generate_greedy_batch: " + err); return -6; }
-    for (int k = 0; k < n; ++k) {
-        for (int j = 0; j + 1 < n_gen; ++j) out[(size_t)k * n_gen + j] = h[(size_t)k * n_gen + j];
-        out[(size_t)k * n_gen + n_gen - 1] = (llama_token)key_token(keys.data() + (size_t)k * kArgSlots);
-        set_seq_past(c, seqs[k], pos0[k] + n_gen);
-    }
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, c.ev0, c.ev1);
-    c.last_us = ms * 1e3;
-    c.last_bytes = bytes;
-    c.n_outputs = 0;
-    (void)max_end;
-    return n_gen;
+    if (!ctx) { set_err(std::string(name) + ": bad arguments (null context)"); return -1; }
+    return generate_batch(name, ctx, n, seqs, first, pos0, n_gen, out, recs.data(), uniforms);
     API_CATCH(-5)
 }
 

@@ -967,6 +967,94 @@ double llmi_bench_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim,
     API_CATCH(-1.0)
 }
 
+static_assert(LLMI_SAMPLE_MAX_TOP_K == kSampleMaxTopK && LLMI_SAMPLE_MAX_LAST_N == kSampleMaxLastN, "llmi.h limits");
+
+// k_sample alone over crafted rows.  The rows' key slots start as a logits launch leaves
+// them (the raw row's argmax key, here in slot 5), so a greedy row reads back its argmax
+// and a sampled row shows that the kernel cleared the other slots.
+int32_t llmi_sample_logits(const float* logits, int32_t n_rows, int32_t V, const int32_t* hist, int32_t n_hist,
+                           const struct llmi_sampler_params* params, const double* uniforms, int32_t* token_out,
+                           int32_t* cand_out, int32_t* n_cand_out, float* penalized_out, double* us_out) {
+    const std::string who = "llmi_sample_logits: ";
+    if (!logits || !params || !uniforms || !token_out || !cand_out || !n_cand_out || (n_hist > 0 && !hist)) {
+        set_err(who + "bad arguments (null pointer)");
+        return -1;
+    }
+    if (n_rows <= 0 || n_rows > kMaxBatch) { set_err(who + "bad arguments (n_rows 1..8)"); return -1; }
+    if (V <= 0 || n_hist < 0) { set_err(who + "bad arguments (V, n_hist)"); return -1; }
+    std::vector<SampleRec> recs((size_t)n_rows);
+    for (int r = 0; r < n_rows; ++r) {
+        const llmi_sampler_params& p = params[r];
+        std::string why;
+        if (!sample_rec_make(p.temperature, p.top_k, p.top_p, p.min_p, p.repeat_penalty, p.repeat_last_n, p.presence_penalty,
+                             p.frequency_penalty, recs[(size_t)r], why)) {
+            set_err(who + "params[" + std::to_string(r) + "]: " + why + " (the device sampler's limits)");
+            return -1;
+        }
+    }
+    API_TRY
+    DevPool P;
+    const size_t nv = (size_t)n_rows * V, nh = (size_t)n_rows * n_hist;
+    float* d_lg = P.get<float>(nv * 4, false);
+    int32_t* d_hist = P.get<int32_t>(nh * 4);
+    double* d_uni = P.get<double>((size_t)n_rows * 8, false);
+    SampleRec* d_rec = P.get<SampleRec>((size_t)n_rows * sizeof(SampleRec), false);
+    int32_t* d_cand = P.get<int32_t>((size_t)n_rows * kSampleMaxTopK * 4);
+    int32_t* d_nc = P.get<int32_t>((size_t)n_rows * 4);
+    StepState* d_st = P.get<StepState>((size_t)n_rows * sizeof(StepState), false);
+    if (P.err != hipSuccess) { set_err(who + "out of device memory"); return -2; }
+    std::vector<StepState> hs((size_t)n_rows);
+    const int pos = n_hist - 1;
+    for (int r = 0; r < n_rows; ++r) {
+        StepState& s = hs[(size_t)r];
+        memset(&s, 0, sizeof s);
+        s.pos = pos;
+        s.pos_next = pos + 1;
+        unsigned long long best = 0;
+        for (int i = 0; i < V; ++i) {  // argmax_key (mv_device.h) on the host
+            float v = logits[(size_t)r * V + i];
+            if (v == 0.f) v = 0.f;
+            uint32_t u;
+            memcpy(&u, &v, 4);
+            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+            const unsigned long long k = ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (uint32_t)i);
+            best = k > best ? k : best;
+        }
+        s.key[pos & 1][5] = best;
+        recs[(size_t)r].uni = d_uni + r;
+        recs[(size_t)r].pos0 = pos;
+        recs[(size_t)r].n_uni = 1;
+    }
+    hipError_t e = hipMemcpy(d_lg, logits, nv * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nh) e = hipMemcpy(d_hist, hist, nh * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_uni, uniforms, (size_t)n_rows * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rec, recs.data(), (size_t)n_rows * sizeof(SampleRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_st, hs.data(), (size_t)n_rows * sizeof(StepState), hipMemcpyHostToDevice);
+    SampleArgs a;
+    a.logits = d_lg; a.V = V; a.st = d_st; a.hist = d_hist; a.hist_stride = (size_t)n_hist; a.rec = d_rec;
+    a.cand = d_cand; a.n_cand = d_nc;
+    HipObjs h;
+    double us = 0.0;
+    if (e == hipSuccess) e = time_launch(h, [&] { return launch_sample(a, n_rows, nullptr); }, us);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    std::vector<float> rows(penalized_out ? nv : 0);
+    if (e == hipSuccess) e = hipMemcpy(hs.data(), d_st, (size_t)n_rows * sizeof(StepState), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(cand_out, d_cand, (size_t)n_rows * kSampleMaxTopK * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(n_cand_out, d_nc, (size_t)n_rows * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && penalized_out) e = hipMemcpy(rows.data(), d_lg, nv * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_err(who + hip_err(e)); return -3; }
+    for (int r = 0; r < n_rows; ++r) {
+        token_out[r] = key_token(hs[(size_t)r].key[pos & 1]);
+        for (int j = 0; penalized_out && j < n_hist; ++j) {
+            const int32_t tok = hist[(size_t)r * n_hist + j];
+            penalized_out[(size_t)r * n_hist + j] = tok >= 0 && tok < V ? rows[(size_t)r * V + tok] : 0.f;
+        }
+    }
+    if (us_out) *us_out = us;
+    return 0;
+    API_CATCH(-5)
+}
+
 // Experiment hook (LLMI_EXP_TRACE builds): one STORE matvec launch with per-wave
 // s_memrealtime stamps {entry, after prologue, first pair done, exit, HW_ID, XCC<<32|pairs}
 // written to trace_dev[grid*waves*6]; returns the grid size, < 0 on error.

@@ -75,7 +75,9 @@ Context::~Context() {
     if (m) (void)hipSetDevice(device);
     for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : bgraphs) (void)hipGraphExecDestroy(g.second);
-    void* bufs[] = {x, q, att, h, logits, scores, rope, kc0, vc0, st0, hist0, pf_tok, pf_x, pf_q, pf_att, pf_h, pf_aq, pf_abs, pf_ad, pf_abf, pf_wsc,
+    for (auto& g : sgraphs) (void)hipGraphExecDestroy(g.second);
+    for (auto& g : sbgraphs) (void)hipGraphExecDestroy(g.second);
+    void* bufs[] = {srec, suni, x, q, att, h, logits, scores, rope, kc0, vc0, st0, hist0, pf_tok, pf_x, pf_q, pf_att, pf_h, pf_aq, pf_abs, pf_ad, pf_abf, pf_wsc,
                     bx, bq, batt, bh, blogits, bscores, btpos, btseq, baq, babs, bad, babf, le_cnt, le_trace};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -598,7 +600,33 @@ static bool exp_prepare(const Model& m) {
 }
 #endif
 
-bool step_enqueue(Context& c, int kv_bound, std::string& err) {
+bool sample_prepare(Context& c, int n, const SampleRec* recs, const int* pos0, const double* uniforms, int n_gen,
+                    std::string& err) {
+    if (!c.srec) HIPC(hipMalloc(&c.srec, sizeof(SampleRec) * kMaxBatch));
+    if (n_gen > c.suni_cap) {  // the records carry the buffer's address: no graph holds it
+        HIPC(hipStreamSynchronize(c.stream));
+        if (c.suni) (void)hipFree(c.suni);
+        c.suni = nullptr;
+        c.suni_cap = 0;
+        const int cap = std::max(64, n_gen);
+        HIPC(hipMalloc(&c.suni, sizeof(double) * kMaxBatch * cap));
+        c.suni_cap = cap;
+    }
+    c.srec_host.assign((size_t)kMaxBatch, SampleRec());
+    c.suni_host.assign(uniforms, uniforms + (size_t)n * n_gen);
+    for (int k = 0; k < n; ++k) {
+        SampleRec& r = c.srec_host[(size_t)k];
+        r = recs[k];
+        r.uni = c.suni + (size_t)k * n_gen;
+        r.pos0 = pos0[k];
+        r.n_uni = n_gen;
+    }
+    HIPC(hipMemcpyAsync(c.suni, c.suni_host.data(), sizeof(double) * n * n_gen, hipMemcpyHostToDevice, c.stream));
+    HIPC(hipMemcpyAsync(c.srec, c.srec_host.data(), sizeof(SampleRec) * kMaxBatch, hipMemcpyHostToDevice, c.stream));
+    return true;
+}
+
+bool step_enqueue(Context& c, int kv_bound, std::string& err, bool sampled) {
     const Model& m = *c.m;
     const HParams& hp = m.hp;
     const int E = hp.n_embd, D = hp.head_dim, nq = hp.n_head * D, nk = hp.n_head_kv * D;
@@ -756,22 +784,30 @@ bool step_enqueue(Context& c, int kv_bound, std::string& err) {
     LLMI_RUN(K_OUTPUT, launch_matvec(lo, EPI_LOGITS, c.max_blocks, c.stream));
     if (P) P->add(K_OUTPUT, (double)m.output.bytes + 8.0 * E + 4.0 * hp.n_vocab);
 #undef LLMI_RUN
+    if (sampled) {  // the sampler chain over this step's logits: the key slots then hold the sampled token
+        SampleArgs sa;
+        sa.logits = c.logits; sa.V = hp.n_vocab; sa.st = c.st; sa.hist = c.hist; sa.rec = c.srec;
+        const hipError_t e = launch_sample(sa, 1, c.stream);
+        if (e != hipSuccess) { err = "launch_sample: " + hip_err(e); return false; }
+    }
     return true;
 }
 
-bool step_run(Context& c, int pos, std::string& err) {
+bool step_run(Context& c, int pos, std::string& err, bool sampled) {
 #if defined(LLMI_EXPERIMENTS)
     if (!exp_prepare(*c.m)) { err = "exp_img"; return false; }
 #endif
     const int kv_bound = kv_bucket_bound(pos + 1, c.n_ctx);
-    if (!c.use_graphs) return step_enqueue(c, kv_bound, err);
+    if (!c.use_graphs) return step_enqueue(c, kv_bound, err, sampled);
     const int bucket = pos / 256;
     const int gkey = bucket * 256 + c.cur_seq;
-    auto it = c.graphs.find(gkey);
-    if (it == c.graphs.end()) {
-        hipGraphExec_t ex = capture_graph(c.stream, [&](std::string& e) { return step_enqueue(c, kv_bound, e); }, err);
+    auto& graphs = sampled ? c.sgraphs : c.graphs;
+    auto it = graphs.find(gkey);
+    if (it == graphs.end()) {
+        hipGraphExec_t ex =
+            capture_graph(c.stream, [&](std::string& e) { return step_enqueue(c, kv_bound, e, sampled); }, err);
         if (!ex) return false;
-        it = c.graphs.emplace(gkey, ex).first;
+        it = graphs.emplace(gkey, ex).first;
     }
     HIPC(hipGraphLaunch(it->second, c.stream));
     return true;
@@ -815,7 +851,7 @@ static bool balloc(Context& c, std::string& err) {
     return true;
 }
 
-static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std::string& err) {
+static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std::string& err, bool sampled) {
     const Model& m = *c.m;
     const HParams& hp = m.hp;
     const int E = hp.n_embd, D = hp.head_dim, QD = hp.n_head * D, nk = hp.n_head_kv * D, F = hp.n_ff, V = hp.n_vocab;
@@ -905,6 +941,12 @@ static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std
     lo.nw = (const float*)(m.arena + m.out_norm.off_a); lo.eps = hp.eps; lo.y = c.blogits; lo.y_stride = V;
     lo.npairs = (V + 1) / 2;
     { bool q = false; BC(bmv(lo, EPI_LOGITS, q)); }
+    if (sampled) {  // one launch for every slot; a slot whose record says greedy keeps its argmax keys
+        SampleArgs sa;
+        sa.logits = c.blogits; sa.V = V; sa.st = c.st0; sa.hist = c.hist0; sa.hist_stride = (size_t)c.n_ctx;
+        sa.tseq = c.btseq; sa.rec = c.srec;
+        BC(launch_sample(sa, nt, c.stream));
+    }
 #undef BC
     return true;
 }
@@ -914,7 +956,7 @@ static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std
 // rows with 4 working waves per workgroup, batch.hip mvn_work_waves).  A layer whose
 // ffn_gate and ffn_up differ in type has no batched step in any numerics (bstep_run's
 // error; llama_decode then steps such sequences one at a time)
-bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err) {
+bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, bool sampled) {
     const HParams& hp = c.m->hp;
     if (nt < 1 || nt > kMaxBatch || c.n_seq < 2) { err = "batched step: 1..8 slots of a context with n_seq_max >= 2"; return false; }
     for (const Layer& L : c.m->layers)
@@ -934,15 +976,16 @@ bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& er
         HIPC(hipStreamSynchronize(c.stream));
         c.btseq_host = map;
     }
-    if (!c.use_graphs) return bstep_enqueue(c, nt, seqs, kv_bound, err);
+    if (!c.use_graphs) return bstep_enqueue(c, nt, seqs, kv_bound, err, sampled);
     std::string key = std::to_string(bucket) + ":" + std::to_string(nt);
     for (int s = 0; s < nt; ++s) key += "," + std::to_string(seqs[s]);
-    auto it = c.bgraphs.find(key);
-    if (it == c.bgraphs.end()) {
+    auto& graphs = sampled ? c.sbgraphs : c.bgraphs;
+    auto it = graphs.find(key);
+    if (it == graphs.end()) {
         hipGraphExec_t ex =
-            capture_graph(c.stream, [&](std::string& e) { return bstep_enqueue(c, nt, seqs, kv_bound, e); }, err);
+            capture_graph(c.stream, [&](std::string& e) { return bstep_enqueue(c, nt, seqs, kv_bound, e, sampled); }, err);
         if (!ex) return false;
-        it = c.bgraphs.emplace(key, ex).first;
+        it = graphs.emplace(key, ex).first;
     }
     HIPC(hipGraphLaunch(it->second, c.stream));
     return true;

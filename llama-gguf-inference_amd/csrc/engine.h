@@ -123,6 +123,16 @@ struct Context {
     void* babf = nullptr;          // k_bmm: the step's bsum pairs as sumi MFMA fragments (pf_abf_off)
     std::vector<int> btseq_host;            // the slot -> sequence map btseq holds
     std::map<std::string, hipGraphExec_t> bgraphs;  // by (slots, sequences, KV bucket)
+    // device sampling (sample.hip): the slots' sampler records and this call's uniforms, filled
+    // by sample_prepare before the steps; the sampled step graphs (a greedy step + k_sample)
+    // are cached apart from the greedy ones
+    SampleRec* srec = nullptr;              // [kMaxBatch]
+    double* suni = nullptr;                 // [kMaxBatch][suni_cap]
+    int suni_cap = 0;
+    std::vector<SampleRec> srec_host;       // what the pending copies read, alive until the call's sync
+    std::vector<double> suni_host;
+    std::map<int, hipGraphExec_t> sgraphs;
+    std::map<std::string, hipGraphExec_t> sbgraphs;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     unsigned* fault_dev = nullptr;          // device fault word: a bounded in-kernel wait gave up
     unsigned* fault_host = nullptr;         // pinned copy, read back with every decode call
@@ -170,11 +180,16 @@ void context_select_seq(Context& c, int s);
 void context_clear_seq(Context& c, int s);
 // one batched decode step of nt sequences seqs[0..nt) (their StepStates hold token and
 // position), replayed from a graph per (slots, sequences, KV bucket of max_pos)
-bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err);
+// (sampled: the step ends with k_sample over its logits rows, sample.hip)
+bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, bool sampled = false);
 // enqueue one decode step for a state already set (token_in/pos_next); kv_bound >= pos+1
-bool step_enqueue(Context& c, int kv_bound, std::string& err);
+bool step_enqueue(Context& c, int kv_bound, std::string& err, bool sampled = false);
 // run one step via the cached graph of its KV bucket (or eagerly)
-bool step_run(Context& c, int pos, std::string& err);
+bool step_run(Context& c, int pos, std::string& err, bool sampled = false);
+// uploads slot k's record recs[k] (k < n; the other slots greedy) and its n_gen uniforms
+// uniforms[k * n_gen ..], drawn by the steps at positions pos0[k] .., on c.stream
+bool sample_prepare(Context& c, int n, const SampleRec* recs, const int* pos0, const double* uniforms, int n_gen,
+                    std::string& err);
 double bytes_per_token(const Model& m, int n_kv);
 // batched prefill: can the model's layers run through the MFMA prefill path?  (flash-
 // attention numerics: only with LLMI_FA_PREFILL=1, read on every call)

@@ -383,4 +383,39 @@ hipError_t launch_arena_hash(const void* p, size_t bytes, unsigned long long* ou
 hipError_t launch_state_set(StepState* st, int token_in, int pos_next, hipStream_t stream);
 hipError_t launch_state_tick(StepState* st, hipStream_t stream);  // seq += 1 (microbenchmarks)
 
+// Sampler chain on the device (sample.hip, k_sample): llmi/sampling.py's
+// sample_with_uniform over a step's logits row, the chosen token left in the step's argmax
+// key slots so that k_embed / k_bembed / key_token read it as they read an argmax.
+constexpr int kSampleMaxTopK = 256;   // 1 <= top_k <= this on the device path
+constexpr int kSampleMaxLastN = 256;  // 0 <= repeat_last_n <= this
+enum : int { SAMPLE_GREEDY = 0,       // the row's argmax keys stay as the logits launch left them
+             SAMPLE_ARGMAX = 1,       // temperature <= 0 with penalties: argmax of the penalized row
+             SAMPLE_DIST = 2 };       // the whole chain, one uniform
+// One slot's sampler record, in device memory and rewritten by every generate call (a
+// replayed graph bakes its kernel arguments in: nothing that varies per call is one).
+struct SampleRec {
+    double temperature = 0, top_p = 1, min_p = 0, repeat_penalty = 1, presence_penalty = 0, frequency_penalty = 0;
+    const double* uni = nullptr;  // the slot's uniforms of this call: step at position p draws uni[p - pos0]
+    int32_t top_k = 1, repeat_last_n = 0;
+    int32_t mode = SAMPLE_GREEDY;
+    int32_t penalized = 0;
+    int32_t pos0 = 0, n_uni = 0;
+};
+struct SampleArgs {
+    float* logits = nullptr;        // slot s's row at logits + s * V; a sampled row is left penalized
+    int V = 0;
+    StepState* st = nullptr;        // slot s's state: st[tseq ? tseq[s] : s]
+    const int32_t* hist = nullptr;  // its token history: hist + (tseq ? tseq[s] : s) * hist_stride, [0, st->pos] valid
+    size_t hist_stride = 0;
+    const int* tseq = nullptr;
+    const SampleRec* rec = nullptr; // [slots]
+    int32_t* cand = nullptr;        // test hook: the final candidate ids [slots][kSampleMaxTopK] ...
+    int32_t* n_cand = nullptr;      // ... and their number [slots] (null in the step graphs)
+};
+// the record of a parameter set (mode and penalized derived as sampling.py derives them);
+// false and `why` naming the field when the device path does not take it
+bool sample_rec_make(double temperature, int top_k, double top_p, double min_p, double repeat_penalty, int repeat_last_n,
+                     double presence_penalty, double frequency_penalty, SampleRec& r, std::string& why);
+hipError_t launch_sample(const SampleArgs& a, int slots, hipStream_t stream);
+
 }  // namespace llmi

@@ -297,6 +297,44 @@ class Model:
             pass
 
 
+def sampler_params(params: Sequence):
+    """A ctypes array of llmi_sampler_params from SamplingParams-like objects."""
+    from ._lib import llmi_sampler_params
+
+    arr = (llmi_sampler_params * len(params))()
+    for a, p in zip(arr, params):
+        a.temperature, a.top_p, a.min_p = float(p.temperature), float(p.top_p), float(p.min_p)
+        a.repeat_penalty, a.presence_penalty = float(p.repeat_penalty), float(p.presence_penalty)
+        a.frequency_penalty, a.top_k, a.repeat_last_n = float(p.frequency_penalty), int(p.top_k), int(p.repeat_last_n)
+    return arr
+
+
+def sample_logits(logits, history, params: Sequence, uniforms, want_penalized: bool = True):
+    """llmi_sample_logits: k_sample alone over crafted rows.  logits [rows][V] f32, history
+    [rows][n_hist] int32 (n_hist may be 0), params one SamplingParams per row, uniforms
+    [rows].  Returns (tokens, candidates, penalized, usec): the chosen token per row, each
+    row's final candidate ids (empty for a greedy row), the rows' values at their history
+    tokens after the kernel, and the launch's device microseconds."""
+    from ._lib import SAMPLE_MAX_TOP_K
+
+    lg = np.ascontiguousarray(np.asarray(logits, dtype=np.float32))
+    rows, V = lg.shape
+    hist = np.ascontiguousarray(np.asarray(history, dtype=np.int32).reshape(rows, -1))
+    n_hist = hist.shape[1]
+    un = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64).reshape(rows))
+    tok = np.zeros(rows, dtype=np.int32)
+    cand = np.zeros((rows, SAMPLE_MAX_TOP_K), dtype=np.int32)
+    ncand = np.zeros(rows, dtype=np.int32)
+    pen = np.zeros((rows, n_hist), dtype=np.float32)
+    us = C.c_double()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    r = lib().llmi_sample_logits(vp(lg), rows, V, vp(hist) if n_hist else None, n_hist, sampler_params(params), vp(un),
+                                 vp(tok), vp(cand), vp(ncand), vp(pen) if want_penalized else None, C.byref(us))
+    if r != 0:
+        raise LlmiError(f"llmi_sample_logits returned {r}: {last_error()}")
+    return ([int(t) for t in tok], [[int(c) for c in cand[i, :ncand[i]]] for i in range(rows)], pen, us.value)
+
+
 class Context:
     """llama_init_from_model: KV cache + scratch + step graphs on the model's device."""
 
@@ -388,6 +426,22 @@ class Context:
         r = lib().llmi_generate_greedy_batch(self._h, k, sa, fa, pa, int(n), out)
         if r != n:
             raise LlmiError(f"llmi_generate_greedy_batch returned {r}: {last_error()}")
+        return [list(out[i * n:(i + 1) * n]) for i in range(k)]
+
+    def generate_sampled_batch(self, seqs: Sequence[int], first: Sequence[int], pos0: Sequence[int], n: int,
+                               params: Sequence, uniforms) -> list[list[int]]:
+        """llmi_generate_sampled_batch: generate_greedy_batch with each sequence's sampler
+        chain (params[k]: a SamplingParams) run on the device after every step; uniforms[k]
+        holds sequence k's n draws (ignored for a greedy chain).  Tokens equal
+        sampling.sample_with_uniform on each step's logits."""
+        k = len(seqs)
+        sa, fa, pa = (C.c_int32 * k)(*seqs), (C.c_int32 * k)(*first), (C.c_int32 * k)(*pos0)
+        un = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64).reshape(k, n))
+        out = (C.c_int32 * (k * n))()
+        r = lib().llmi_generate_sampled_batch(self._h, k, sa, fa, pa, int(n), sampler_params(params),
+                                              un.ctypes.data_as(C.POINTER(C.c_double)), out)
+        if r != n:
+            raise LlmiError(f"llmi_generate_sampled_batch returned {r}: {last_error()}")
         return [list(out[i * n:(i + 1) * n]) for i in range(k)]
 
     def seq_rm(self, seq: int, p0: int = 0, p1: int = -1) -> bool:

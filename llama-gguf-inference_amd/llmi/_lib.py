@@ -82,6 +82,23 @@ class llmi_epilogue_args(C.Structure):
 
 EPI_QKV, EPI_SWIGLU, EPI_LOGITS = 2, 3, 4  # LLMI_EPI_*
 
+
+class llmi_sampler_params(C.Structure):
+    """One sequence's sampler chain (include/llmi.h)."""
+    _fields_ = [
+        ("temperature", C.c_double),
+        ("top_p", C.c_double),
+        ("min_p", C.c_double),
+        ("repeat_penalty", C.c_double),
+        ("presence_penalty", C.c_double),
+        ("frequency_penalty", C.c_double),
+        ("top_k", C.c_int32),
+        ("repeat_last_n", C.c_int32),
+    ]
+
+
+SAMPLE_MAX_TOP_K, SAMPLE_MAX_LAST_N = 256, 256  # LLMI_SAMPLE_MAX_*
+
 # name -> (restype, argtypes); every entry point declared in include/llmi.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -127,6 +144,11 @@ SIGNATURES = {
     "llmi_generate_greedy": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "llmi_generate_greedy_batch": (C.c_int32, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
+    "llmi_generate_sampled_batch": (C.c_int32, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int32), C.c_int32, C.POINTER(llmi_sampler_params),
+                                                C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "llmi_sample_logits": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(llmi_sampler_params), _P, _P, _P,
+                                       _P, _P, C.POINTER(C.c_double)]),
     "llama_kv_self_seq_rm": (C.c_bool, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "llmi_seq_pos_max": (C.c_int32, [_P, C.c_int32]),
     "llmi_model_upload_s": (C.c_double, [_P]),

@@ -26,7 +26,12 @@ repeat, presence and frequency penalties / seed per request, llama-server's defa
 `stop` strings end the generation (the text stops before them); `ignore_eos` and
 `n_predict` follow llama-server; `n` > 1 and `logprobs` are rejected with a 400.
 Greedy requests (temperature 0 or top_k 1, no penalties) decode on the device with
-on-device argmax feedback; sampled ones copy each step's logits to the host.  Every GPU
+on-device argmax feedback.  Sampled requests within the device sampler's limits (top_k
+1..256, a penalty window of at most 256 tokens) join them in the same batched call: the
+chain runs on the device logits (llmi_generate_sampled_batch), driven by uniforms drawn
+from the request's seeded generator, and only their first token after prefill is sampled
+on the host.  Other sampled requests, and all of them with LLMI_DEVICE_SAMPLING=0 (read
+when a replica starts; A/B), copy each step's logits to the host sampler.  Every GPU
 replica is one llmi Context with `--parallel` sequences (llama-server's slots) driven by
 one scheduler thread: requests go to the least-loaded replica and are decoded there
 together, one batched step per token for up to 8 sequences (continuous batching,
@@ -49,7 +54,12 @@ import uuid
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from typing import Callable, Iterable, Optional
 
-from .sampling import Sampler, SamplingParams, StopFilter, find_stop, parse_stop
+import numpy as np
+
+from .sampling import Sampler, SamplingParams, StopFilter, device_eligible, find_stop, parse_stop
+
+# a greedy slot of a sampled batched call: the chain that is an argmax of the raw logits
+_GREEDY = SamplingParams(temperature=0.0, top_k=1, top_p=1.0, min_p=0.0)
 
 VERSION = "llmi-server 0.1 (libllmi, gfx950)"
 
@@ -182,7 +192,8 @@ class TextCodec:
 # --------------------------------------------------------------------------------------
 class Request:
     """One generation: prompt ids in, token lists out through `q` (None terminates).
-    `sampling` None or greedy: device argmax; else a host Sampler over each step's logits.
+    `sampling` None or greedy: device argmax; else a Sampler: its chain runs on the device
+    fed by its generator's uniforms, or on the host over each step's logits (Replica._step).
     `stop`: strings that end the generation (checked on the detokenized output)."""
 
     def __init__(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
@@ -239,6 +250,8 @@ class Replica:
         self.last_gbps = 0.0     # HBM GB/s of the last decode call (algorithmic bytes / device time)
         self.requests = 0
         self.stop = False
+        # device sampling: the context has the call, and LLMI_DEVICE_SAMPLING is not 0
+        self.device_sampling = hasattr(ctx, "generate_sampled_batch") and os.environ.get("LLMI_DEVICE_SAMPLING", "1") != "0"
         self.th = threading.Thread(target=self._run, name=f"llmi-replica-{idx}", daemon=True)
         self.th.start()
 
@@ -332,9 +345,28 @@ class Replica:
         c = self.ctx
         t0 = time.perf_counter()
         greedy = [r for r in batch if r.sampler is None]
-        sampled = [r for r in batch if r.sampler is not None]
+        ondev = [r for r in batch if r.sampler is not None and self.device_sampling and device_eligible(r.sampler.p)]
+        sampled = [r for r in batch if r.sampler is not None and r not in ondev]
         outs: dict[int, list[int]] = {}
-        if greedy:
+        if ondev:
+            # sampled requests within the device sampler's limits and the greedy ones advance
+            # k tokens in one call (one weight pass per step for all of them): each sampled
+            # request's chain runs on the device logits, fed the next k draws of its own
+            # generator -- the draws the host path would make, so a seed gives the same text
+            # on either path (draws past a request's end are discarded with it)
+            group = greedy + ondev
+            params = [_GREEDY] * len(greedy) + [r.sampler.p for r in ondev]
+            unis = [np.zeros(k)] * len(greedy) + [r.sampler.rng.random(k) if r.sampler.p.temperature > 0.0 else np.zeros(k)
+                                                  for r in ondev]
+            try:
+                got = c.generate_sampled_batch([r.seq for r in group], [r.last for r in group], [r.pos for r in group],
+                                               k, params, unis)
+            except Exception:  # not batchable here: one sequence at a time, same results
+                got = [c.generate_sampled_batch([r.seq], [r.last], [r.pos], k, [p], [u])[0]
+                       for r, p, u in zip(group, params, unis)]
+            for r, toks in zip(group, got):
+                outs[id(r)] = toks
+        elif greedy:
             # greedy slots decode k tokens per call with the argmax fed back on the device,
             # whether or not sampled requests share the replica
             try:
