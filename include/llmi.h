@@ -255,7 +255,7 @@ int32_t llmi_profile_kernels(struct llama_context* ctx, llama_token first, int32
  *                     xspin_limit 0: every such wait gives up at once; fault-path test)
  *   "numerics"        this thread's numerics for the kernel-level entry points below
  *                     (llmi_repack's byte order, llmi_matvec, llmi_bmv, llmi_mv_epilogue,
- *                     llmi_quantize_act,
+ *                     llmi_quantize_act, llmi_step_entry,
  *                     llmi_attention, llmi_battention, llmi_pf_attention,
  *                     llmi_pf_attention_fa):
  *                     LLMI_NUMERICS_* */
@@ -341,7 +341,11 @@ int32_t llmi_debug_tap(struct llama_context* ctx, int32_t which, float* out);
  * All pointers are DEVICE pointers on the current HIP device; the call is enqueued
  * on the NULL stream and synchronised.  Types are ggml type ids (Q4_K=12, Q5_K=13,
  * Q6_K=14, Q8_0=8).  `w_dev` holds the weight in llmi's device layout produced by
- * llmi_repack (identity for Q4_K/Q5_K/F32).  Return 0 on success. */
+ * llmi_repack (identity for Q4_K/Q5_K/F32).  Return 0 on success.
+ * The kernels address a matrix's planes with 32-bit byte offsets: llmi_device_layout_bytes
+ * and llmi_repack refuse (< 0, llmi_last_error set; no device call) a quantized matrix whose
+ * quant plane (128 B per K-quant block, 32 B per Q8_0 block) reaches 4 GiB, as the model
+ * loader does. */
 int64_t llmi_device_layout_bytes(int32_t type, int64_t rows, int64_t cols);
 int32_t llmi_repack(int32_t type, const void* raw_dev, void* w_dev, int64_t rows, int64_t cols);
 /* y = W . quantize(norm_w ? rmsnorm(x)*norm_w : x); mode 0 store, 1 accumulate (y += .) */
@@ -434,6 +438,51 @@ struct llmi_epilogue_args {
     int32_t* pos_next_out;
 };
 int32_t llmi_mv_epilogue(const struct llmi_epilogue_args* args);
+/* One step-entry launch at kernel level (no model): the kernel every decode step, batched
+ * step and prefill starts with -- the token choice (the host token, or the 64-lane maximum
+ * over the previous step's argmax key slots), the state hand-off (pos, token, seq, the
+ * cleared key parity, hist, tpos) and get_rows from the device layout (dequant_elem).
+ *
+ * kernel  0  launch_embed (k_embed): one slot, one state
+ *         1  launch_bembed (k_bembed): nt (1..8) slots over n_seq (nt..64) states, slot s
+ *            the step of sequence tseq[s] (host, distinct)
+ *         2  launch_pf_embed (k_pf_embed): nt (1..65535) tokens from `tokens` (host) at
+ *            positions pos0.. (pos0 >= 0); no state
+ *         3  launch_embed_row (k_embed_row, llmi_debug_tap 0): reads states[0].token only
+ * w_dev is the [vocab][cols] weight in device layout (llmi_repack), its byte order this
+ * thread's "numerics" test option.  All other pointers are HOST memory.  In and out:
+ * states [n_seq] (kernels 0 / 1 / 3; every field and all 2 x 64 key slots are the
+ * caller's), hist [n_seq][n_ctx] (kernels 0 / 1 / 2; n_seq = 1 but for kernel 1), tpos [8]
+ * (kernel 1).  Out: x_out [slots][cols], the f32 bits, slots = 8 for kernel 1, nt for
+ * kernel 2, else 1; the rows start as LLMI_STEP_SENTINEL, so a slot the launch does not
+ * write keeps it.  The hook's device buffers of x, hist and the states lie between guard
+ * regions filled with LLMI_STEP_SENTINEL; guard_bad [3] returns the number of guard words
+ * of each that changed (0: no write outside the buffer).  Only the kernel asked for runs.
+ * Bad arguments (a null pointer, an unknown type, cols no positive multiple of 256, vocab
+ * <= 0, nt or n_seq outside the kernel's range, a tseq entry repeated or outside
+ * 0..n_seq-1, n_ctx outside 1..2^20, pos0 < 0, kernel outside 0..3, a weight whose quant
+ * plane reaches 4 GiB) are rejected before any device call.  0 on success. */
+#define LLMI_STEP_SENTINEL 0x7FC5A5A5u
+struct llmi_step_state {        /* the device's StepState */
+    int32_t token_in, token_in_pos, pos_next, pos, token;
+    uint32_t seq;
+    uint64_t key[2][64];
+};
+struct llmi_step_entry_args {
+    int32_t kernel, type;
+    const void* w_dev;
+    int64_t vocab, cols;
+    int32_t nt, n_seq, n_ctx;
+    int32_t pos0;               /* kernel 2 */
+    const int32_t* tseq;        /* kernel 1: [nt] */
+    const int32_t* tokens;      /* kernel 2: [nt] */
+    struct llmi_step_state* states;
+    int32_t* hist;
+    int32_t* tpos;
+    uint32_t* x_out;
+    int32_t* guard_bad;
+};
+int32_t llmi_step_entry(const struct llmi_step_entry_args* args);
 /* the activation quantization the matvec prologue performs, written out in ggml block
  * form (block_q8_K for K-quant weight types, block_q8_0 for Q8_0) for bit-exact checks */
 int32_t llmi_quantize_act(int32_t type, int64_t cols, const float* x_dev, const float* norm_w_dev,

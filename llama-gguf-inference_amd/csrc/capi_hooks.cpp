@@ -314,6 +314,10 @@ static Seg seg_at(int32_t type, const void* w, int64_t rows, int64_t cols) {
 
 int64_t llmi_device_layout_bytes(int32_t type, int64_t rows, int64_t cols) {
     if (!type_supported(type) || cols % block_elems(type)) return -1;
+    if (rows > 0 && cols > 0 && !planes_fit_u32(type, rows, cols)) {
+        set_err(std::string("llmi_device_layout_bytes: ") + kPlaneLimitMsg);
+        return -1;
+    }
     DevMat dm;
     dm.type = type; dm.rows = rows; dm.cols = cols;
     return (int64_t)plan_planes(dm, 0);
@@ -321,6 +325,10 @@ int64_t llmi_device_layout_bytes(int32_t type, int64_t rows, int64_t cols) {
 
 int32_t llmi_repack(int32_t type, const void* raw, void* w, int64_t rows, int64_t cols) {
     if (!type_supported(type) || cols % block_elems(type)) { set_err("bad type/shape"); return -1; }
+    if (rows > 0 && cols > 0 && !planes_fit_u32(type, rows, cols)) {
+        set_err(std::string("llmi_repack: ") + kPlaneLimitMsg);
+        return -1;
+    }
     DevMat dm;
     dm.type = type; dm.rows = rows; dm.cols = cols;
     plan_planes(dm, 0);
@@ -643,6 +651,124 @@ int32_t llmi_mv_epilogue(const struct llmi_epilogue_args* A) {
         }
     }
     if (e != hipSuccess) { set_err(std::string("llmi_mv_epilogue: ") + hip_err(e)); return -2; }
+    return 0;
+    API_CATCH(-5)
+}
+
+static_assert(sizeof(llmi_step_state) == sizeof(StepState) && offsetof(llmi_step_state, key) == offsetof(StepState, key) &&
+                  offsetof(llmi_step_state, seq) == offsetof(StepState, seq),
+              "llmi_step_state mirrors StepState");
+
+int32_t llmi_step_entry(const struct llmi_step_entry_args* A) {
+    auto bad = [](const char* what) {
+        set_err(std::string("llmi_step_entry: ") + what);
+        return -1;
+    };
+    if (!A) return bad("null arguments");
+    const int kernel = A->kernel, nt = A->nt, n_seq = A->n_seq, n_ctx = A->n_ctx;
+    if (kernel < 0 || kernel > 3) return bad("kernel outside 0..3");
+    if (!weight_type_ok(A->type)) return bad("unknown weight type");
+    if (!A->w_dev) return bad("null weight");
+    if (A->cols <= 0 || A->cols > INT32_MAX || A->cols % 256) return bad("cols must be a positive multiple of 256");
+    if (A->vocab <= 0 || A->vocab > INT32_MAX) return bad("vocab out of range");
+    if (!planes_fit_u32(A->type, A->vocab, A->cols)) return bad(kPlaneLimitMsg);
+    if (kernel == 1 ? (nt < 1 || nt > kMaxBatch) : kernel == 2 ? (nt < 1 || nt > 65535) : nt != 1)
+        return bad("nt out of range (kernels 0 / 3: 1, kernel 1: 1..8, kernel 2: 1..65535)");
+    if (kernel == 1 ? (n_seq < nt || n_seq > 64) : n_seq != 1) return bad("n_seq out of range (kernel 1: nt..64, else 1)");
+    if (n_ctx <= 0 || n_ctx > (1 << 20)) return bad("n_ctx outside 1..2^20");
+    if (kernel == 1) {
+        if (!A->tseq || !A->tpos) return bad("null tseq / tpos");
+        for (int s = 0; s < nt; ++s) {
+            if (A->tseq[s] < 0 || A->tseq[s] >= n_seq) return bad("tseq outside 0..n_seq-1");
+            for (int r = 0; r < s; ++r)
+                if (A->tseq[r] == A->tseq[s]) return bad("tseq names a sequence twice");
+        }
+    }
+    if (kernel == 2) {
+        if (!A->tokens) return bad("null tokens");
+        if (A->pos0 < 0 || A->pos0 > INT32_MAX - nt) return bad("pos0 out of range");
+    } else if (!A->states) {
+        return bad("null states");
+    }
+    if (kernel != 3 && !A->hist) return bad("null hist");
+    if (!A->x_out || !A->guard_bad) return bad("null x_out / guard_bad");
+    API_TRY
+    const int cols = (int)A->cols, vocab = (int)A->vocab;
+    const size_t slots = kernel == 1 ? (size_t)kMaxBatch : kernel == 2 ? (size_t)nt : 1;
+    constexpr size_t G = 1024;  // guard words before and after each buffer
+    DevPool P;
+    // a device buffer of `words` 32-bit words between two guards, everything the sentinel but
+    // the `init` words copied in
+    struct Guarded {
+        uint32_t* dev = nullptr;
+        size_t words = 0;
+        std::vector<uint32_t> host;
+        uint32_t* body() { return dev + G; }
+    };
+    auto make = [&](Guarded& g, size_t words, const void* init) {
+        g.words = words;
+        g.host.assign(words + 2 * G, LLMI_STEP_SENTINEL);
+        if (init) memcpy(g.host.data() + G, init, words * 4);
+        g.dev = P.get<uint32_t>(g.host.size() * 4, false);
+        if (g.dev) P.err = hipMemcpy(g.dev, g.host.data(), g.host.size() * 4, hipMemcpyHostToDevice);
+    };
+    // back to the host: the body into `out`, the guards counted
+    auto fetch = [&](Guarded& g, void* out, int32_t& nbad) -> hipError_t {
+        nbad = 0;
+        if (!g.dev) return hipSuccess;
+        const hipError_t e = hipMemcpy(g.host.data(), g.dev, g.host.size() * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        for (size_t i = 0; i < G; ++i)
+            nbad += (g.host[i] != LLMI_STEP_SENTINEL) + (g.host[G + g.words + i] != LLMI_STEP_SENTINEL);
+        if (out) memcpy(out, g.host.data() + G, g.words * 4);
+        return hipSuccess;
+    };
+    Guarded gx, gh, gs;
+    make(gx, slots * (size_t)cols, nullptr);
+    if (kernel != 3) make(gh, (size_t)n_seq * n_ctx, A->hist);
+    if (kernel != 2) make(gs, (size_t)n_seq * sizeof(StepState) / 4, A->states);
+    int hmap[2 * kMaxBatch] = {};  // [0, 8): tpos, [8, 16): tseq
+    int* dmap = nullptr;
+    int32_t* dtok = nullptr;
+    if (kernel == 1) {
+        for (int s = 0; s < kMaxBatch; ++s) hmap[s] = A->tpos[s];
+        for (int s = 0; s < nt; ++s) hmap[kMaxBatch + s] = A->tseq[s];
+        dmap = P.get<int>(sizeof(hmap), false);
+        if (dmap) P.err = hipMemcpy(dmap, hmap, sizeof(hmap), hipMemcpyHostToDevice);
+    } else if (kernel == 2) {
+        dtok = P.get<int32_t>((size_t)nt * 4, false);
+        if (dtok) P.err = hipMemcpy(dtok, A->tokens, (size_t)nt * 4, hipMemcpyHostToDevice);
+    }
+    hipError_t e = P.err;
+    const Seg w = seg_at(A->type, A->w_dev, vocab, cols);
+    if (e == hipSuccess && (kernel == 0 || kernel == 3)) {
+        EmbArgs ea;
+        ea.w = w; ea.cols = cols; ea.vocab = vocab; ea.n_ctx = n_ctx;
+        ea.x = (float*)gx.body();
+        ea.st = (StepState*)gs.body();
+        ea.hist = kernel == 0 ? (int32_t*)gh.body() : nullptr;
+        e = kernel == 0 ? launch_embed(ea, nullptr) : launch_embed_row(ea, ea.st, ea.x, nullptr);
+    } else if (e == hipSuccess && kernel == 1) {
+        BEmbArgs ba;
+        ba.w = w; ba.cols = cols; ba.vocab = vocab; ba.n_ctx = n_ctx; ba.nt = nt;
+        ba.x = (float*)gx.body();
+        ba.st = (StepState*)gs.body();
+        ba.hist = (int32_t*)gh.body();
+        ba.tseq = dmap + kMaxBatch;
+        ba.tpos = dmap;
+        e = launch_bembed(ba, nullptr);
+    } else if (e == hipSuccess) {
+        e = launch_pf_embed(w, cols, vocab, dtok, (float*)gx.body(), nt, (int32_t*)gh.body(), A->pos0, n_ctx, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = fetch(gx, A->x_out, A->guard_bad[0]);
+    if (e == hipSuccess) e = fetch(gh, A->hist, A->guard_bad[1]);
+    if (e == hipSuccess) e = fetch(gs, A->states, A->guard_bad[2]);
+    if (e == hipSuccess && kernel == 1) {
+        e = hipMemcpy(hmap, dmap, sizeof(hmap), hipMemcpyDeviceToHost);
+        for (int s = 0; s < kMaxBatch && e == hipSuccess; ++s) A->tpos[s] = hmap[s];
+    }
+    if (e != hipSuccess) { set_err(std::string("llmi_step_entry: ") + hip_err(e)); return -2; }
     return 0;
     API_CATCH(-5)
 }

@@ -125,6 +125,15 @@ inline size_t plan_planes(DevMat& m, size_t base) {
     }
 }
 inline bool needs_repack(int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0; }
+// piece_off (mv_device.h) and the kernels' plane offsets are 32-bit: the largest plane of a
+// repacked matrix, A (128 B per K-quant block, 32 B per Q8_0 block), must end below 4 GiB.
+// rows, cols > 0.
+constexpr const char* kPlaneLimitMsg = "the matrix's quant plane reaches 4 GiB (32-bit piece offsets)";
+inline bool planes_fit_u32(int t, int64_t rows, int64_t cols) {
+    if (!needs_repack(t)) return true;
+    const int64_t per_row = cols / block_elems(t) * (t == T_Q8_0 ? 32 : 128);
+    return per_row < ((int64_t)1 << 32) && rows <= (((int64_t)1 << 32) - 1) / (per_row > 0 ? per_row : 1);
+}
 
 // On-device decode state (one per context).  Step s at position p:
 //   k_embed (every workgroup): p = pos_next; token = (token_in_pos == p) ? token_in

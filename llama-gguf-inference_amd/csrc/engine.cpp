@@ -222,6 +222,7 @@ bool model_load(const std::string& path, int device, bool vocab_only, bool no_up
             return false;
         }
         if (!quant && m.type != T_F32) { err = std::string(nm) + ": norm weight must be f32"; return false; }
+        if (quant && !planes_fit_u32(m.type, rows, cols)) { err = std::string(nm) + ": " + kPlaneLimitMsg; return false; }
         return true;
     };
     if (!chk(M.out_norm, 1, E, "output_norm", false)) return false;

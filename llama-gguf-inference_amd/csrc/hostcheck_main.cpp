@@ -1,5 +1,5 @@
 // hostcheck_main.cpp — the host-only C ABI (capi_host.cpp, gguf.cpp, tokenizer.cpp,
-// synth_writer.cpp) as a plain host program for the address and undefined-behaviour
+// synth_writer.cpp) and common.h's plane-limit arithmetic as a plain host program for the address and undefined-behaviour
 // sanitizers: `make hostcheck`.  No HIP, no device.  Exits 0 when every check holds.
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +12,7 @@
 #include <unistd.h>
 
 #include "../../include/llmi.h"
+#include "common.h"
 
 #define CHECK(c)                                                           \
     do {                                                                   \
@@ -67,6 +68,16 @@ int main() {
     }
     CHECK(!llmi_vocab_load_from_file(cut.c_str()) && llmi_last_error()[0]);
     CHECK(llmi_synth_write_gguf((d + "/x.gguf").c_str(), "no-such-preset", 1, 1, 0, 1) < 0 && llmi_last_error()[0]);
+
+    // the 4 GiB bound of the 32-bit piece offsets (common.h; the hooks and the loader refuse
+    // by it): exact at the edge, and no signed overflow at the largest shapes an int takes
+    using llmi::planes_fit_u32;
+    CHECK(!planes_fit_u32(llmi::T_Q4_K, 1 << 17, 65536) && planes_fit_u32(llmi::T_Q4_K, (1 << 17) - 1, 65536));
+    CHECK(!planes_fit_u32(llmi::T_Q6_K, 1 << 25, 256) && planes_fit_u32(llmi::T_Q6_K, (1 << 25) - 1, 256));
+    CHECK(!planes_fit_u32(llmi::T_Q8_0, 1 << 20, 4096) && planes_fit_u32(llmi::T_Q8_0, (1 << 20) - 1, 4096));
+    CHECK(!planes_fit_u32(llmi::T_Q5_K, INT32_MAX, (int64_t)INT32_MAX / 256 * 256));
+    CHECK(!planes_fit_u32(llmi::T_Q8_0, INT64_MAX / 2, (int64_t)1 << 40) && planes_fit_u32(llmi::T_F32, INT32_MAX, INT32_MAX));
+    CHECK(planes_fit_u32(llmi::T_Q4_K, 128256, 8192) && llmi::layout_rgs(llmi::T_Q4_K, 1004, 512) == 2);
 
     for (const auto& f : files) unlink(f.path.c_str());
     unlink(cut.c_str());

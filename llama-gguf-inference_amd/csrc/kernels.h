@@ -127,7 +127,7 @@ size_t le_counter_stride(int n_layer);  // words
 hipError_t layer_engine_prepare(LeArgs& a);
 hipError_t launch_layer_engine(const LeArgs& a, hipStream_t s);  // a prepared
 double le_stream_bench(const void* src, size_t bytes, int mode, int iters, int nt);  // GB/s (tools/lestream.py)
-bool le_wanted();                 // LLMI_ENGINE (default 1) / test option "engine"
+bool le_wanted();                 // LLMI_ENGINE (default 0) / test option "engine"
 extern int g_le_on, g_le_spin;    // test options: engine on/off, spin limit
 
 struct AttnArgs {

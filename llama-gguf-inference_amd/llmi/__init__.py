@@ -335,6 +335,50 @@ def sample_logits(logits, history, params: Sequence, uniforms, want_penalized: b
     return ([int(t) for t in tok], [[int(c) for c in cand[i, :ncand[i]]] for i in range(rows)], pen, us.value)
 
 
+# the device's StepState (llmi_step_state) as a NumPy record
+STEP_STATE = np.dtype([("token_in", "<i4"), ("token_in_pos", "<i4"), ("pos_next", "<i4"), ("pos", "<i4"), ("token", "<i4"),
+                       ("seq", "<u4"), ("key", "<u8", (2, 64))])
+
+
+def step_entry(kernel: int, qtype: int, w_dev: int, vocab: int, cols: int, n_ctx: int, states=None, hist=None, tseq=None,
+               tpos=None, tokens=None, pos0: int = 0):
+    """llmi_step_entry: one step-entry launch (kernel 0 k_embed, 1 k_bembed, 2 k_pf_embed, 3
+    k_embed_row) over the [vocab][cols] weight at device address w_dev.  states: STEP_STATE
+    records, one per sequence (kernels 0 / 1 / 3); hist int32 [n_seq][n_ctx] (kernels 0 / 1 /
+    2); tseq the slots' sequences and tpos int32 [8] (kernel 1); tokens and pos0 (kernel 2).
+    The inputs are left alone.  Returns (x, states, hist, tpos, guard_bad): x uint32
+    [slots][cols] (the f32 bits; a slot the launch did not write holds STEP_SENTINEL), the
+    states, hist and tpos after the launch (None where the kernel has none), and the
+    changed guard words of the hook's x, hist and state buffers."""
+    from ._lib import llmi_step_entry_args, llmi_step_state
+
+    a = llmi_step_entry_args()
+    a.kernel, a.type, a.w_dev, a.vocab, a.cols, a.n_ctx, a.pos0 = kernel, qtype, w_dev, vocab, cols, n_ctx, pos0
+    i32p = lambda v: v.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+    st = hs = tp = ts = tk = None
+    a.n_seq = 1
+    if kernel != 2:
+        st = np.array(states, dtype=STEP_STATE).reshape(-1)
+        a.states, a.n_seq = st.ctypes.data_as(C.POINTER(llmi_step_state)), len(st)
+    if kernel != 3:
+        hs = np.array(hist, dtype=np.int32).reshape(a.n_seq, n_ctx)
+        a.hist = i32p(hs)
+    a.nt = 1
+    if kernel == 1:
+        ts, tp = np.array(tseq, dtype=np.int32).reshape(-1), np.array(tpos, dtype=np.int32).reshape(8)
+        a.tseq, a.tpos, a.nt = i32p(ts), i32p(tp), len(ts)
+    elif kernel == 2:
+        tk = np.array(tokens, dtype=np.int32).reshape(-1)
+        a.tokens, a.nt = i32p(tk), len(tk)
+    x = np.zeros((8 if kernel == 1 else a.nt, cols), dtype=np.uint32)
+    bad = np.full(3, -1, dtype=np.int32)
+    a.x_out, a.guard_bad = x.ctypes.data_as(C.POINTER(C.c_uint32)), i32p(bad)
+    r = lib().llmi_step_entry(C.byref(a))
+    if r != 0:
+        raise LlmiError(f"llmi_step_entry returned {r}: {last_error()}")
+    return x, st, hs, tp, [int(b) for b in bad]
+
+
 class Context:
     """llama_init_from_model: KV cache + scratch + step graphs on the model's device."""
 

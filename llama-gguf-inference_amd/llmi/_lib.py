@@ -83,6 +83,46 @@ class llmi_epilogue_args(C.Structure):
 EPI_QKV, EPI_SWIGLU, EPI_LOGITS = 2, 3, 4  # LLMI_EPI_*
 
 
+class llmi_step_state(C.Structure):
+    """The device's StepState (include/llmi.h)."""
+    _fields_ = [
+        ("token_in", C.c_int32),
+        ("token_in_pos", C.c_int32),
+        ("pos_next", C.c_int32),
+        ("pos", C.c_int32),
+        ("token", C.c_int32),
+        ("seq", C.c_uint32),
+        ("key", (C.c_uint64 * 64) * 2),
+    ]
+
+
+class llmi_step_entry_args(C.Structure):
+    """llmi_step_entry's arguments (include/llmi.h): w_dev a device pointer as an integer,
+    everything else host memory."""
+    _fields_ = [
+        ("kernel", C.c_int32),
+        ("type", C.c_int32),
+        ("w_dev", C.c_void_p),
+        ("vocab", C.c_int64),
+        ("cols", C.c_int64),
+        ("nt", C.c_int32),
+        ("n_seq", C.c_int32),
+        ("n_ctx", C.c_int32),
+        ("pos0", C.c_int32),
+        ("tseq", C.POINTER(C.c_int32)),
+        ("tokens", C.POINTER(C.c_int32)),
+        ("states", C.POINTER(llmi_step_state)),
+        ("hist", C.POINTER(C.c_int32)),
+        ("tpos", C.POINTER(C.c_int32)),
+        ("x_out", C.POINTER(C.c_uint32)),
+        ("guard_bad", C.POINTER(C.c_int32)),
+    ]
+
+
+STEP_SENTINEL = 0x7FC5A5A5  # LLMI_STEP_SENTINEL
+STEP_EMBED, STEP_BEMBED, STEP_PF_EMBED, STEP_EMBED_ROW = 0, 1, 2, 3  # llmi_step_entry's kernels
+
+
 class llmi_sampler_params(C.Structure):
     """One sequence's sampler chain (include/llmi.h)."""
     _fields_ = [
@@ -193,6 +233,7 @@ SIGNATURES = {
     "llmi_matvec": (C.c_int32, [C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, _P, C.c_int32]),
     "llmi_bmv": (C.c_int32, [C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_int32, _P, C.c_int32]),
     "llmi_mv_epilogue": (C.c_int32, [C.POINTER(llmi_epilogue_args)]),
+    "llmi_step_entry": (C.c_int32, [C.POINTER(llmi_step_entry_args)]),
     "llmi_quantize_act": (C.c_int32, [C.c_int32, C.c_int64, _P, _P, C.c_float, _P]),
     "llmi_bench_stream": (C.c_double, [_P, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
     "llmi_bench_matvec": (C.c_double, [C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32]),
