@@ -212,6 +212,24 @@ struct llmi_sampler_params {
 int32_t llmi_generate_sampled_batch(struct llama_context* ctx, int32_t n, const int32_t* seqs, const llama_token* first,
                                     const int32_t* pos0, int32_t n_gen, const struct llmi_sampler_params* params,
                                     const double* uniforms, llama_token* out);
+/* llmi_generate_sampled_batch that also reports log-probabilities under each step's RAW
+ * distribution (no penalties, no temperature; llmi/sampling.py's token_logprobs: x[t] - lse
+ * with lse the row's logsumexp in FP64), computed on the device next to the sampler
+ * (k_logprob, k_logprob_pick): no logits leave the device.  n_top[k] is -1 (nothing for
+ * sequence k: its output entries are left untouched) or 0 .. LLMI_LOGPROBS_MAX_TOP, the number
+ * of alternatives (0: the chosen token's log-probability only).  tok_logprob[k * n_gen + j] is
+ * the log-probability of out[k * n_gen + j]; top_id / top_logprob [(k * n_gen + j) *
+ * LLMI_LOGPROBS_MAX_TOP + i] are step j's i-th most likely token (logit descending, lower id
+ * first on ties) and its log-probability, entries from min(n_top[k], n_vocab) on holding id -1
+ * and -inf.  out is bit-identical to llmi_generate_sampled_batch's for the same arguments.
+ * Arguments, return codes, bounded waits and fault read-back as that call; an n_top outside
+ * -1 .. LLMI_LOGPROBS_MAX_TOP or a null pointer is refused with -1 before any device work,
+ * the error naming the field. */
+#define LLMI_LOGPROBS_MAX_TOP 20
+int32_t llmi_generate_logprobs_batch(struct llama_context* ctx, int32_t n, const int32_t* seqs, const llama_token* first,
+                                     const int32_t* pos0, int32_t n_gen, const struct llmi_sampler_params* params,
+                                     const double* uniforms, const int32_t* n_top, llama_token* out, double* tok_logprob,
+                                     int32_t* top_id, double* top_logprob);
 /* seconds the weight upload took in llama_model_load_from_file (chunked pinned H2D,
  * double-buffered against the on-device repack; file reads included) */
 double llmi_model_upload_s(const struct llama_model* model);
@@ -585,6 +603,19 @@ int32_t llmi_trace_matvec(int32_t type, const void* w_dev, int64_t rows, int64_t
 int32_t llmi_sample_logits(const float* logits, int32_t n_rows, int32_t V, const int32_t* hist, int32_t n_hist,
                            const struct llmi_sampler_params* params, const double* uniforms, int32_t* token_out,
                            int32_t* cand_out, int32_t* n_cand_out, float* penalized_out, double* us_out);
+/* What a step with log-probabilities launches after its logits, in step order: k_logprob,
+ * k_sample, k_logprob_pick, no model.  logits, hist, params, uniforms as llmi_sample_logits
+ * (rows at stride V: an odd V leaves rows off a 16-byte boundary); n_top [n_rows] each -1 or
+ * 0 .. LLMI_LOGPROBS_MAX_TOP.  Out, all HOST memory: token_out [n_rows]; tok_logprob_out and
+ * lse_out [n_rows]; top_id_out and top_logprob_out [n_rows][LLMI_LOGPROBS_MAX_TOP]; rows_out
+ * [n_rows][V] the rows after the three kernels (NULL: not wanted); us_out [3] (optional) the
+ * event-timed microseconds of k_logprob, k_sample and k_logprob_pick.  A row with n_top -1
+ * keeps the caller's values in its logprob outputs.  Arguments are checked before any device
+ * call.  Returns 0 or < 0. */
+int32_t llmi_logprob_rows(const float* logits, int32_t n_rows, int32_t V, const int32_t* hist, int32_t n_hist,
+                          const struct llmi_sampler_params* params, const double* uniforms, const int32_t* n_top,
+                          int32_t* token_out, double* tok_logprob_out, double* lse_out, int32_t* top_id_out,
+                          double* top_logprob_out, float* rows_out, double* us_out);
 
 #pragma GCC visibility pop
 

@@ -43,10 +43,24 @@ void set_seq_past(Context& c, int s, int v) {
     else c.seq_past[(size_t)s] = v;
 }
 
+// where llmi_generate_logprobs_batch wants its results: n_top per sequence (-1: nothing for it)
+struct LogprobOut {
+    const int32_t* n_top;
+    double* tok_lp;   // [n][n_gen]
+    int32_t* top_id;  // [n][n_gen][kLogprobMaxTop]
+    double* top_lp;
+};
+void logprob_readback_seq(Context& c, const LogprobOut& lp, int k, int n_gen) {
+    if (lp.n_top[k] < 0) return;  // its entries stay as the caller left them
+    const size_t at = (size_t)k * n_gen;
+    logprob_readback(c, k, n_gen, lp.tok_lp + at, lp.top_id + at * kLogprobMaxTop, lp.top_lp + at * kLogprobMaxTop);
+}
+
 // llmi_generate_greedy's body; sampled: the steps end with k_sample (the caller has uploaded
-// the records and uniforms, sample_prepare)
+// the records and uniforms, sample_prepare); lp: and with the logprob kernels around it
+// (logprob_prepare), slot 0's results read back with the tokens
 int32_t generate_one(const char* name, llama_context* ctx, llama_token first, int32_t pos0, int32_t n_gen, llama_token* out,
-                     bool sampled) {
+                     bool sampled, const LogprobOut* lp = nullptr) {
     const std::string who = std::string(name) + ": ";
     if (!ctx || !out || n_gen <= 0) { set_err(who + "bad arguments"); return -1; }
     Context& c = ctx->c;
@@ -60,7 +74,7 @@ int32_t generate_one(const char* name, llama_context* ctx, llama_token first, in
     if (launch_state_set(c.st, first, pos0, c.stream) != hipSuccess) { set_err("state set failed"); return -3; }
     hipEventRecord(c.ev0, c.stream);
     for (int k = 0; k < n_gen; ++k) {
-        if (!step_run(c, pos0 + k, err, sampled)) {
+        if (!step_run(c, pos0 + k, err, lp ? STEP_LOGPROBS : sampled ? STEP_SAMPLED : STEP_GREEDY)) {
             if (sampled) (void)hipStreamSynchronize(c.stream);  // sample_prepare's copies read the context's host vectors
             set_err(who + err);
             return -3;
@@ -73,6 +87,7 @@ int32_t generate_one(const char* name, llama_context* ctx, llama_token first, in
     if (n_gen > 1)
         (void)hipMemcpyAsync(h.data(), c.hist + pos0 + 1, (size_t)(n_gen - 1) * 4, hipMemcpyDeviceToHost, c.stream);
     (void)hipMemcpyAsync(keys, &c.st->key[(pos0 + n_gen - 1) & 1][0], sizeof(keys), hipMemcpyDeviceToHost, c.stream);
+    if (lp) logprob_readback_seq(c, *lp, 0, n_gen);
     context_fault_readback(c);
     hipError_t e = hipStreamSynchronize(c.stream);
     if (e != hipSuccess) { set_err(who + hip_err(e)); return -4; }
@@ -89,9 +104,10 @@ int32_t generate_one(const char* name, llama_context* ctx, llama_token first, in
 }
 
 // llmi_generate_greedy_batch's body; recs (n records) and uniforms (n x n_gen) non-null: the
-// sampled call, every step ending with k_sample
+// sampled call, every step ending with k_sample; lp non-null as well: the call with logprobs
 int32_t generate_batch(const char* name, llama_context* ctx, int32_t n, const int32_t* seqs, const llama_token* first,
-                       const int32_t* pos0, int32_t n_gen, llama_token* out, const SampleRec* recs, const double* uniforms) {
+                       const int32_t* pos0, int32_t n_gen, llama_token* out, const SampleRec* recs, const double* uniforms,
+                       const LogprobOut* lp = nullptr) {
     const std::string who = std::string(name) + ": ";
     const bool sampled = recs != nullptr;
     if (!ctx || n <= 0 || n > kMaxBatch || !seqs || !first || !pos0 || !out || n_gen <= 0) {
@@ -111,9 +127,14 @@ int32_t generate_batch(const char* name, llama_context* ctx, int32_t n, const in
     (void)hipGetLastError();
     std::string err;
     if (sampled && !sample_prepare(c, n, recs, pos0, uniforms, n_gen, err)) { set_err(who + err); return -3; }
+    if (lp && !logprob_prepare(c, n, lp->n_top, pos0, n_gen, err)) {
+        (void)hipStreamSynchronize(c.stream);
+        set_err(who + err);
+        return -3;
+    }
     if (n == 1) {  // one sequence: the single-sequence step (k_matvec path, its own graphs)
         context_select_seq(c, seqs[0]);
-        return generate_one(name, ctx, first[0], pos0[0], n_gen, out, sampled);
+        return generate_one(name, ctx, first[0], pos0[0], n_gen, out, sampled, lp);
     }
     double bytes = 0;
     for (int k = 0; k < n; ++k)
@@ -129,7 +150,7 @@ int32_t generate_batch(const char* name, llama_context* ctx, int32_t n, const in
             max_pos = std::max(max_pos, pos0[k] + j);
             bytes += bytes_per_token(*c.m, pos0[k] + j + 1) / n;
         }
-        if (!bstep_run(c, n, seqs, max_pos, err, sampled)) {
+        if (!bstep_run(c, n, seqs, max_pos, err, lp ? STEP_LOGPROBS : sampled ? STEP_SAMPLED : STEP_GREEDY)) {
             // (a model without a batched step ends here; the caller may call again at once, and
             // sample_prepare's pending copies still read the context's host vectors)
             if (sampled) (void)hipStreamSynchronize(c.stream);
@@ -147,6 +168,7 @@ int32_t generate_batch(const char* name, llama_context* ctx, int32_t n, const in
                                  c.stream);
         (void)hipMemcpyAsync(keys.data() + (size_t)k * kArgSlots, &c.st0[seqs[k]].key[(pos0[k] + n_gen - 1) & 1][0],
                              8 * kArgSlots, hipMemcpyDeviceToHost, c.stream);
+        if (lp) logprob_readback_seq(c, *lp, k, n_gen);
     }
     context_fault_readback(c);
     hipError_t e = hipStreamSynchronize(c.stream);
@@ -529,6 +551,45 @@ int32_t llmi_generate_sampled_batch(struct llama_context* ctx, int32_t n, const 
     }
     if (!ctx) { set_err(std::string(name) + ": bad arguments (null context)"); return -1; }
     return generate_batch(name, ctx, n, seqs, first, pos0, n_gen, out, recs.data(), uniforms);
+    API_CATCH(-5)
+}
+
+static_assert(LLMI_LOGPROBS_MAX_TOP == kLogprobMaxTop, "llmi.h limits");
+
+int32_t llmi_generate_logprobs_batch(struct llama_context* ctx, int32_t n, const int32_t* seqs, const llama_token* first,
+                                     const int32_t* pos0, int32_t n_gen, const struct llmi_sampler_params* params,
+                                     const double* uniforms, const int32_t* n_top, llama_token* out, double* tok_logprob,
+                                     int32_t* top_id, double* top_logprob) {
+    API_TRY
+    const std::string name = "llmi_generate_logprobs_batch";
+    // what needs no context first: refusals name their field before any device work
+    if (n <= 0 || n > kMaxBatch || n_gen <= 0) { set_err(name + ": bad arguments (1..8 sequences, n_gen >= 1)"); return -1; }
+    const struct { const char* field; const void* p; } ptrs[] = {
+        {"seqs", seqs}, {"first", first}, {"pos0", pos0}, {"params", params}, {"uniforms", uniforms}, {"n_top", n_top},
+        {"out", out}, {"tok_logprob", tok_logprob}, {"top_id", top_id}, {"top_logprob", top_logprob}};
+    for (const auto& f : ptrs)
+        if (!f.p) { set_err(name + ": " + f.field + " is a null pointer"); return -1; }
+    for (int k = 0; k < n; ++k)
+        for (int j = 0; j < k; ++j)
+            if (seqs[j] == seqs[k]) { set_err(name + ": seqs: repeated sequence"); return -1; }
+    std::vector<SampleRec> recs((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const llmi_sampler_params& p = params[k];
+        std::string why;
+        if (!sample_rec_make(p.temperature, p.top_k, p.top_p, p.min_p, p.repeat_penalty, p.repeat_last_n, p.presence_penalty,
+                             p.frequency_penalty, recs[(size_t)k], why)) {
+            set_err(name + ": params[" + std::to_string(k) + "]: " + why + " (the device sampler's limits)");
+            return -1;
+        }
+        if (n_top[k] < -1 || n_top[k] > kLogprobMaxTop) {
+            set_err(name + ": n_top[" + std::to_string(k) + "] " + std::to_string(n_top[k]) + " outside -1.." +
+                    std::to_string(kLogprobMaxTop));
+            return -1;
+        }
+    }
+    if (!ctx) { set_err(name + ": ctx is a null pointer"); return -1; }
+    const LogprobOut lp = {n_top, tok_logprob, top_id, top_logprob};
+    return generate_batch(name.c_str(), ctx, n, seqs, first, pos0, n_gen, out, recs.data(), uniforms, &lp);
     API_CATCH(-5)
 }
 

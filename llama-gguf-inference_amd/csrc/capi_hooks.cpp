@@ -1181,6 +1181,119 @@ int32_t llmi_sample_logits(const float* logits, int32_t n_rows, int32_t V, const
     API_CATCH(-5)
 }
 
+// The tail of a step with log-probabilities over crafted rows: k_logprob, k_sample,
+// k_logprob_pick in step order.  Key slots as llmi_sample_logits sets them.
+int32_t llmi_logprob_rows(const float* logits, int32_t n_rows, int32_t V, const int32_t* hist, int32_t n_hist,
+                          const struct llmi_sampler_params* params, const double* uniforms, const int32_t* n_top,
+                          int32_t* token_out, double* tok_logprob_out, double* lse_out, int32_t* top_id_out,
+                          double* top_logprob_out, float* rows_out, double* us_out) {
+    const std::string who = "llmi_logprob_rows: ";
+    if (!logits || !params || !uniforms || !n_top || !token_out || !tok_logprob_out || !lse_out || !top_id_out ||
+        !top_logprob_out || (n_hist > 0 && !hist)) {
+        set_err(who + "bad arguments (null pointer)");
+        return -1;
+    }
+    if (n_rows <= 0 || n_rows > kMaxBatch) { set_err(who + "bad arguments (n_rows 1..8)"); return -1; }
+    if (V <= 0 || n_hist < 0) { set_err(who + "bad arguments (V, n_hist)"); return -1; }
+    std::vector<SampleRec> recs((size_t)n_rows);
+    for (int r = 0; r < n_rows; ++r) {
+        const llmi_sampler_params& p = params[r];
+        std::string why;
+        if (!sample_rec_make(p.temperature, p.top_k, p.top_p, p.min_p, p.repeat_penalty, p.repeat_last_n, p.presence_penalty,
+                             p.frequency_penalty, recs[(size_t)r], why)) {
+            set_err(who + "params[" + std::to_string(r) + "]: " + why + " (the device sampler's limits)");
+            return -1;
+        }
+        if (n_top[r] < -1 || n_top[r] > kLogprobMaxTop) {
+            set_err(who + "n_top[" + std::to_string(r) + "] outside -1.." + std::to_string(kLogprobMaxTop));
+            return -1;
+        }
+    }
+    API_TRY
+    DevPool P;
+    const size_t nv = (size_t)n_rows * V, nh = (size_t)n_rows * n_hist, nr = (size_t)n_rows;
+    float* d_lg = P.get<float>(nv * 4, false);
+    int32_t* d_hist = P.get<int32_t>(nh * 4);
+    double* d_uni = P.get<double>(nr * 8, false);
+    SampleRec* d_rec = P.get<SampleRec>(nr * sizeof(SampleRec), false);
+    LogprobRec* d_lrec = P.get<LogprobRec>(nr * sizeof(LogprobRec), false);
+    StepState* d_st = P.get<StepState>(nr * sizeof(StepState), false);
+    double* d_lse = P.get<double>(nr * 8);
+    double* d_tok = P.get<double>(nr * 8);
+    double* d_top = P.get<double>(nr * kLogprobMaxTop * 8);
+    int32_t* d_top_id = P.get<int32_t>(nr * kLogprobMaxTop * 4);
+    int32_t* d_wtok = P.get<int32_t>(nr * kSampleMaxLastN * 4);
+    float* d_wraw = P.get<float>(nr * kSampleMaxLastN * 4);
+    if (P.err != hipSuccess) { set_err(who + "out of device memory"); return -2; }
+    std::vector<StepState> hs(nr);
+    std::vector<LogprobRec> lrecs(nr);
+    const int pos = n_hist - 1;
+    for (int r = 0; r < n_rows; ++r) {
+        StepState& s = hs[(size_t)r];
+        memset(&s, 0, sizeof s);
+        s.pos = pos;
+        s.pos_next = pos + 1;
+        unsigned long long best = 0;
+        for (int i = 0; i < V; ++i) {  // argmax_key (mv_device.h) on the host
+            float v = logits[(size_t)r * V + i];
+            if (v == 0.f) v = 0.f;
+            uint32_t u;
+            memcpy(&u, &v, 4);
+            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+            const unsigned long long k = ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (uint32_t)i);
+            best = k > best ? k : best;
+        }
+        s.key[pos & 1][5] = best;
+        recs[(size_t)r].uni = d_uni + r;
+        recs[(size_t)r].pos0 = pos;
+        recs[(size_t)r].n_uni = 1;
+        LogprobRec& l = lrecs[(size_t)r];
+        l.n_top = n_top[r]; l.pos0 = pos; l.n_step = 1;
+        l.lse = d_lse + r; l.tok_lp = d_tok + r;
+        l.top_lp = d_top + (size_t)r * kLogprobMaxTop; l.top_id = d_top_id + (size_t)r * kLogprobMaxTop;
+        l.win_tok = d_wtok + (size_t)r * kSampleMaxLastN; l.win_raw = d_wraw + (size_t)r * kSampleMaxLastN;
+    }
+    hipError_t e = hipMemcpy(d_lg, logits, nv * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nh) e = hipMemcpy(d_hist, hist, nh * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_uni, uniforms, nr * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rec, recs.data(), nr * sizeof(SampleRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_lrec, lrecs.data(), nr * sizeof(LogprobRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_st, hs.data(), nr * sizeof(StepState), hipMemcpyHostToDevice);
+    SampleArgs a;
+    a.logits = d_lg; a.V = V; a.st = d_st; a.hist = d_hist; a.hist_stride = (size_t)n_hist; a.rec = d_rec;
+    LogprobArgs la;
+    la.logits = d_lg; la.V = V; la.st = d_st; la.hist = d_hist; la.hist_stride = (size_t)n_hist; la.rec = d_rec;
+    la.lrec = d_lrec;
+    HipObjs h;
+    double us[3] = {0.0, 0.0, 0.0};
+    if (e == hipSuccess) e = time_launch(h, [&] { return launch_logprob(la, n_rows, nullptr); }, us[0]);
+    if (e == hipSuccess) e = time_launch(h, [&] { return launch_sample(a, n_rows, nullptr); }, us[1]);
+    if (e == hipSuccess) e = time_launch(h, [&] { return launch_logprob_pick(la, n_rows, nullptr); }, us[2]);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    std::vector<double> lse(nr), tok(nr), top(nr * kLogprobMaxTop);
+    std::vector<int32_t> top_id(nr * kLogprobMaxTop);
+    if (e == hipSuccess) e = hipMemcpy(hs.data(), d_st, nr * sizeof(StepState), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(lse.data(), d_lse, nr * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(tok.data(), d_tok, nr * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(top.data(), d_top, nr * kLogprobMaxTop * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(top_id.data(), d_top_id, nr * kLogprobMaxTop * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rows_out) e = hipMemcpy(rows_out, d_lg, nv * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_err(who + hip_err(e)); return -3; }
+    for (int r = 0; r < n_rows; ++r) {
+        token_out[r] = key_token(hs[(size_t)r].key[pos & 1]);
+        if (n_top[r] < 0) continue;
+        lse_out[r] = lse[(size_t)r];
+        tok_logprob_out[r] = tok[(size_t)r];
+        for (int i = 0; i < kLogprobMaxTop; ++i) {
+            top_id_out[r * kLogprobMaxTop + i] = top_id[(size_t)r * kLogprobMaxTop + i];
+            top_logprob_out[r * kLogprobMaxTop + i] = top[(size_t)r * kLogprobMaxTop + i];
+        }
+    }
+    if (us_out) for (int i = 0; i < 3; ++i) us_out[i] = us[i];
+    return 0;
+    API_CATCH(-5)
+}
+
 // Experiment hook (LLMI_EXP_TRACE builds): one STORE matvec launch with per-wave
 // s_memrealtime stamps {entry, after prologue, first pair done, exit, HW_ID, XCC<<32|pairs}
 // written to trace_dev[grid*waves*6]; returns the grid size, < 0 on error.

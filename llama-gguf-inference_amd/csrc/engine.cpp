@@ -77,7 +77,9 @@ Context::~Context() {
     for (auto& g : bgraphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : sgraphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : sbgraphs) (void)hipGraphExecDestroy(g.second);
-    void* bufs[] = {srec, suni, x, q, att, h, logits, scores, rope, kc0, vc0, st0, hist0, pf_tok, pf_x, pf_q, pf_att, pf_h, pf_aq, pf_abs, pf_ad, pf_abf, pf_wsc,
+    for (auto& g : lgraphs) (void)hipGraphExecDestroy(g.second);
+    for (auto& g : lbgraphs) (void)hipGraphExecDestroy(g.second);
+    void* bufs[] = {srec, suni, lrec, lp_lse, lp_tok, lp_top, lp_top_id, lp_win_tok, lp_win_raw, x, q, att, h, logits, scores, rope, kc0, vc0, st0, hist0, pf_tok, pf_x, pf_q, pf_att, pf_h, pf_aq, pf_abs, pf_ad, pf_abf, pf_wsc,
                     bx, bq, batt, bh, blogits, bscores, btpos, btseq, baq, babs, bad, babf, le_cnt, le_trace};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -627,7 +629,53 @@ bool sample_prepare(Context& c, int n, const SampleRec* recs, const int* pos0, c
     return true;
 }
 
-bool step_enqueue(Context& c, int kv_bound, std::string& err, bool sampled) {
+bool logprob_prepare(Context& c, int n, const int32_t* n_top, const int* pos0, int n_gen, std::string& err) {
+    if (!c.lrec) {
+        HIPC(hipMalloc(&c.lrec, sizeof(LogprobRec) * kMaxBatch));
+        HIPC(hipMalloc(&c.lp_win_tok, sizeof(int32_t) * kMaxBatch * kSampleMaxLastN));
+        HIPC(hipMalloc(&c.lp_win_raw, sizeof(float) * kMaxBatch * kSampleMaxLastN));
+    }
+    if (n_gen > c.lp_cap) {  // the records carry the rings' addresses: no graph holds them
+        HIPC(hipStreamSynchronize(c.stream));
+        void** rings[] = {(void**)&c.lp_lse, (void**)&c.lp_tok, (void**)&c.lp_top, (void**)&c.lp_top_id};
+        for (void** r : rings) {
+            if (*r) (void)hipFree(*r);
+            *r = nullptr;
+        }
+        c.lp_cap = 0;
+        const size_t cap = (size_t)std::max(64, n_gen);
+        HIPC(hipMalloc(&c.lp_lse, sizeof(double) * kMaxBatch * cap));
+        HIPC(hipMalloc(&c.lp_tok, sizeof(double) * kMaxBatch * cap));
+        HIPC(hipMalloc(&c.lp_top, sizeof(double) * kMaxBatch * cap * kLogprobMaxTop));
+        HIPC(hipMalloc(&c.lp_top_id, sizeof(int32_t) * kMaxBatch * cap * kLogprobMaxTop));
+        c.lp_cap = (int)cap;
+    }
+    c.lrec_host.assign((size_t)kMaxBatch, LogprobRec());
+    for (int k = 0; k < n; ++k) {
+        LogprobRec& r = c.lrec_host[(size_t)k];
+        const size_t at = (size_t)k * c.lp_cap;
+        r.n_top = n_top[k];
+        r.pos0 = pos0[k];
+        r.n_step = n_gen;
+        r.lse = c.lp_lse + at;
+        r.tok_lp = c.lp_tok + at;
+        r.top_lp = c.lp_top + at * kLogprobMaxTop;
+        r.top_id = c.lp_top_id + at * kLogprobMaxTop;
+        r.win_tok = c.lp_win_tok + (size_t)k * kSampleMaxLastN;
+        r.win_raw = c.lp_win_raw + (size_t)k * kSampleMaxLastN;
+    }
+    HIPC(hipMemcpyAsync(c.lrec, c.lrec_host.data(), sizeof(LogprobRec) * kMaxBatch, hipMemcpyHostToDevice, c.stream));
+    return true;
+}
+
+void logprob_readback(Context& c, int k, int n_gen, double* tok_lp, int32_t* top_id, double* top_lp) {
+    const size_t at = (size_t)k * c.lp_cap, n = (size_t)n_gen;
+    (void)hipMemcpyAsync(tok_lp, c.lp_tok + at, n * 8, hipMemcpyDeviceToHost, c.stream);
+    (void)hipMemcpyAsync(top_id, c.lp_top_id + at * kLogprobMaxTop, n * kLogprobMaxTop * 4, hipMemcpyDeviceToHost, c.stream);
+    (void)hipMemcpyAsync(top_lp, c.lp_top + at * kLogprobMaxTop, n * kLogprobMaxTop * 8, hipMemcpyDeviceToHost, c.stream);
+}
+
+bool step_enqueue(Context& c, int kv_bound, std::string& err, int tail) {
     const Model& m = *c.m;
     const HParams& hp = m.hp;
     const int E = hp.n_embd, D = hp.head_dim, nq = hp.n_head * D, nk = hp.n_head_kv * D;
@@ -785,28 +833,38 @@ bool step_enqueue(Context& c, int kv_bound, std::string& err, bool sampled) {
     LLMI_RUN(K_OUTPUT, launch_matvec(lo, EPI_LOGITS, c.max_blocks, c.stream));
     if (P) P->add(K_OUTPUT, (double)m.output.bytes + 8.0 * E + 4.0 * hp.n_vocab);
 #undef LLMI_RUN
-    if (sampled) {  // the sampler chain over this step's logits: the key slots then hold the sampled token
+    LogprobArgs la;
+    la.logits = c.logits; la.V = hp.n_vocab; la.st = c.st; la.hist = c.hist; la.rec = c.srec; la.lrec = c.lrec;
+    if (tail == STEP_LOGPROBS) {  // the raw row's logsumexp and alternatives, before the sampler rewrites it
+        const hipError_t e = launch_logprob(la, 1, c.stream);
+        if (e != hipSuccess) { err = "launch_logprob: " + hip_err(e); return false; }
+    }
+    if (tail != STEP_GREEDY) {  // the sampler chain over this step's logits: the key slots then hold the sampled token
         SampleArgs sa;
         sa.logits = c.logits; sa.V = hp.n_vocab; sa.st = c.st; sa.hist = c.hist; sa.rec = c.srec;
         const hipError_t e = launch_sample(sa, 1, c.stream);
         if (e != hipSuccess) { err = "launch_sample: " + hip_err(e); return false; }
     }
+    if (tail == STEP_LOGPROBS) {  // the chosen token's log-probability
+        const hipError_t e = launch_logprob_pick(la, 1, c.stream);
+        if (e != hipSuccess) { err = "launch_logprob_pick: " + hip_err(e); return false; }
+    }
     return true;
 }
 
-bool step_run(Context& c, int pos, std::string& err, bool sampled) {
+bool step_run(Context& c, int pos, std::string& err, int tail) {
 #if defined(LLMI_EXPERIMENTS)
     if (!exp_prepare(*c.m)) { err = "exp_img"; return false; }
 #endif
     const int kv_bound = kv_bucket_bound(pos + 1, c.n_ctx);
-    if (!c.use_graphs) return step_enqueue(c, kv_bound, err, sampled);
+    if (!c.use_graphs) return step_enqueue(c, kv_bound, err, tail);
     const int bucket = pos / 256;
     const int gkey = bucket * 256 + c.cur_seq;
-    auto& graphs = sampled ? c.sgraphs : c.graphs;
+    auto& graphs = tail == STEP_LOGPROBS ? c.lgraphs : tail == STEP_SAMPLED ? c.sgraphs : c.graphs;
     auto it = graphs.find(gkey);
     if (it == graphs.end()) {
         hipGraphExec_t ex =
-            capture_graph(c.stream, [&](std::string& e) { return step_enqueue(c, kv_bound, e, sampled); }, err);
+            capture_graph(c.stream, [&](std::string& e) { return step_enqueue(c, kv_bound, e, tail); }, err);
         if (!ex) return false;
         it = graphs.emplace(gkey, ex).first;
     }
@@ -852,7 +910,7 @@ static bool balloc(Context& c, std::string& err) {
     return true;
 }
 
-static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std::string& err, bool sampled) {
+static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std::string& err, int tail) {
     const Model& m = *c.m;
     const HParams& hp = m.hp;
     const int E = hp.n_embd, D = hp.head_dim, QD = hp.n_head * D, nk = hp.n_head_kv * D, F = hp.n_ff, V = hp.n_vocab;
@@ -942,12 +1000,17 @@ static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std
     lo.nw = (const float*)(m.arena + m.out_norm.off_a); lo.eps = hp.eps; lo.y = c.blogits; lo.y_stride = V;
     lo.npairs = (V + 1) / 2;
     { bool q = false; BC(bmv(lo, EPI_LOGITS, q)); }
-    if (sampled) {  // one launch for every slot; a slot whose record says greedy keeps its argmax keys
+    LogprobArgs la;
+    la.logits = c.blogits; la.V = V; la.st = c.st0; la.hist = c.hist0; la.hist_stride = (size_t)c.n_ctx;
+    la.tseq = c.btseq; la.rec = c.srec; la.lrec = c.lrec;
+    if (tail == STEP_LOGPROBS) BC(launch_logprob(la, nt, c.stream));  // the raw rows, before the sampler
+    if (tail != STEP_GREEDY) {  // one launch for every slot; a slot whose record says greedy keeps its argmax keys
         SampleArgs sa;
         sa.logits = c.blogits; sa.V = V; sa.st = c.st0; sa.hist = c.hist0; sa.hist_stride = (size_t)c.n_ctx;
         sa.tseq = c.btseq; sa.rec = c.srec;
         BC(launch_sample(sa, nt, c.stream));
     }
+    if (tail == STEP_LOGPROBS) BC(launch_logprob_pick(la, nt, c.stream));
 #undef BC
     return true;
 }
@@ -957,7 +1020,7 @@ static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std
 // rows with 4 working waves per workgroup, batch.hip mvn_work_waves).  A layer whose
 // ffn_gate and ffn_up differ in type has no batched step in any numerics (bstep_run's
 // error; llama_decode then steps such sequences one at a time)
-bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, bool sampled) {
+bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, int tail) {
     const HParams& hp = c.m->hp;
     if (nt < 1 || nt > kMaxBatch || c.n_seq < 2) { err = "batched step: 1..8 slots of a context with n_seq_max >= 2"; return false; }
     for (const Layer& L : c.m->layers)
@@ -977,14 +1040,14 @@ bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& er
         HIPC(hipStreamSynchronize(c.stream));
         c.btseq_host = map;
     }
-    if (!c.use_graphs) return bstep_enqueue(c, nt, seqs, kv_bound, err, sampled);
+    if (!c.use_graphs) return bstep_enqueue(c, nt, seqs, kv_bound, err, tail);
     std::string key = std::to_string(bucket) + ":" + std::to_string(nt);
     for (int s = 0; s < nt; ++s) key += "," + std::to_string(seqs[s]);
-    auto& graphs = sampled ? c.sbgraphs : c.bgraphs;
+    auto& graphs = tail == STEP_LOGPROBS ? c.lbgraphs : tail == STEP_SAMPLED ? c.sbgraphs : c.bgraphs;
     auto it = graphs.find(key);
     if (it == graphs.end()) {
         hipGraphExec_t ex =
-            capture_graph(c.stream, [&](std::string& e) { return bstep_enqueue(c, nt, seqs, kv_bound, e, sampled); }, err);
+            capture_graph(c.stream, [&](std::string& e) { return bstep_enqueue(c, nt, seqs, kv_bound, e, tail); }, err);
         if (!ex) return false;
         it = graphs.emplace(key, ex).first;
     }

@@ -133,6 +133,18 @@ struct Context {
     std::vector<double> suni_host;
     std::map<int, hipGraphExec_t> sgraphs;
     std::map<std::string, hipGraphExec_t> sbgraphs;
+    // device log-probabilities (logprob.hip): the slots' records and the output rings they
+    // point into, filled by logprob_prepare; the steps with logprobs (logits, k_logprob,
+    // k_sample, k_logprob_pick) have graphs of their own
+    LogprobRec* lrec = nullptr;             // [kMaxBatch]
+    double *lp_lse = nullptr, *lp_tok = nullptr, *lp_top = nullptr;  // [kMaxBatch][lp_cap] ([kLogprobMaxTop])
+    int32_t* lp_top_id = nullptr;
+    int32_t* lp_win_tok = nullptr;          // [kMaxBatch][kSampleMaxLastN]
+    float* lp_win_raw = nullptr;
+    int lp_cap = 0;
+    std::vector<LogprobRec> lrec_host;
+    std::map<int, hipGraphExec_t> lgraphs;
+    std::map<std::string, hipGraphExec_t> lbgraphs;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     unsigned* fault_dev = nullptr;          // device fault word: a bounded in-kernel wait gave up
     unsigned* fault_host = nullptr;         // pinned copy, read back with every decode call
@@ -180,16 +192,23 @@ void context_select_seq(Context& c, int s);
 void context_clear_seq(Context& c, int s);
 // one batched decode step of nt sequences seqs[0..nt) (their StepStates hold token and
 // position), replayed from a graph per (slots, sequences, KV bucket of max_pos)
-// (sampled: the step ends with k_sample over its logits rows, sample.hip)
-bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, bool sampled = false);
+// (tail STEP_SAMPLED: the step ends with k_sample over its logits rows, sample.hip;
+// STEP_LOGPROBS: with k_logprob before it and k_logprob_pick after it, logprob.hip)
+enum : int { STEP_GREEDY = 0, STEP_SAMPLED = 1, STEP_LOGPROBS = 2 };
+bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, int tail = STEP_GREEDY);
 // enqueue one decode step for a state already set (token_in/pos_next); kv_bound >= pos+1
-bool step_enqueue(Context& c, int kv_bound, std::string& err, bool sampled = false);
+bool step_enqueue(Context& c, int kv_bound, std::string& err, int tail = STEP_GREEDY);
 // run one step via the cached graph of its KV bucket (or eagerly)
-bool step_run(Context& c, int pos, std::string& err, bool sampled = false);
+bool step_run(Context& c, int pos, std::string& err, int tail = STEP_GREEDY);
 // uploads slot k's record recs[k] (k < n; the other slots greedy) and its n_gen uniforms
 // uniforms[k * n_gen ..], drawn by the steps at positions pos0[k] .., on c.stream
 bool sample_prepare(Context& c, int n, const SampleRec* recs, const int* pos0, const double* uniforms, int n_gen,
                     std::string& err);
+// uploads slot k's logprob record (n_top[k], k < n; the other slots -1) for steps at positions
+// pos0[k] .., growing the output rings to n_gen steps, on c.stream
+bool logprob_prepare(Context& c, int n, const int32_t* n_top, const int* pos0, int n_gen, std::string& err);
+// enqueue the copies of slot k's n_gen ring entries to the host arrays (before the call's sync)
+void logprob_readback(Context& c, int k, int n_gen, double* tok_lp, int32_t* top_id, double* top_lp);
 double bytes_per_token(const Model& m, int n_kv);
 // batched prefill: can the model's layers run through the MFMA prefill path?  (flash-
 // attention numerics: only with LLMI_FA_PREFILL=1, read on every call)

@@ -418,4 +418,35 @@ bool sample_rec_make(double temperature, int top_k, double top_p, double min_p, 
                      double presence_penalty, double frequency_penalty, SampleRec& r, std::string& why);
 hipError_t launch_sample(const SampleArgs& a, int slots, hipStream_t stream);
 
+// Token log-probabilities on the device (logprob.hip): llmi/sampling.py's token_logprobs over
+// a step's RAW logits row.  k_logprob runs after the logits launch and before k_sample (which
+// leaves the row penalized): the row's logsumexp in FP64 and its top n_top keys in the
+// sampler's order; k_logprob_pick runs after k_sample and adds the chosen token's
+// log-probability, raw logit - lse.
+constexpr int kLogprobMaxTop = 20;
+// One slot's logprob record, in device memory and rewritten by every generate call like its
+// SampleRec.  The outputs are rings indexed by the step's pos - pos0.
+struct LogprobRec {
+    int32_t n_top = -1;           // -1: the slot wants nothing (both kernels return at once); else 0..kLogprobMaxTop
+    int32_t pos0 = 0, n_step = 0; // steps at positions pos0 .. pos0 + n_step - 1 write
+    double* lse = nullptr;        // [n_step]
+    double* tok_lp = nullptr;     // [n_step] the chosen token's log-probability
+    int32_t* top_id = nullptr;    // [n_step][kLogprobMaxTop]; unused entries -1 ...
+    double* top_lp = nullptr;     // ... and -inf
+    int32_t* win_tok = nullptr;   // [kSampleMaxLastN] this step's penalty window (-1: unused) and the raw
+    float* win_raw = nullptr;     // logits of its tokens, saved before k_sample rewrites them
+};
+struct LogprobArgs {
+    const float* logits = nullptr;  // slot s's row at logits + s * V
+    int V = 0;
+    const StepState* st = nullptr;  // as SampleArgs
+    const int32_t* hist = nullptr;
+    size_t hist_stride = 0;
+    const int* tseq = nullptr;
+    const SampleRec* rec = nullptr;     // [slots] the penalty window's size
+    const LogprobRec* lrec = nullptr;   // [slots]
+};
+hipError_t launch_logprob(const LogprobArgs& a, int slots, hipStream_t stream);
+hipError_t launch_logprob_pick(const LogprobArgs& a, int slots, hipStream_t stream);
+
 }  // namespace llmi

@@ -28,7 +28,7 @@
 //              bits, which the decision margins of the tests bound.)
 //   output     slot 0 of st->key[pos & 1] = the chosen candidate's key, slots 1 .. 63 = 0.
 #include "kernels.h"
-#include "mv_device.h"
+#include "sample_device.h"
 #include "launch_util.h"
 
 #include <cmath>
@@ -36,14 +36,6 @@
 #include <hip/hip_runtime.h>
 
 namespace llmi {
-
-constexpr int kSmpThreads = 1024;
-constexpr int kSmpWaves = kSmpThreads / 64;
-constexpr int kSmpUnroll = 4;    // 16-byte row loads a thread has in flight before it uses the first
-constexpr int kSmpCand = 1024;  // keys gathered into LDS for the sort (>= kSampleMaxTopK, a power of two)
-static_assert(kSmpCand >= kSampleMaxTopK && (kSmpCand & (kSmpCand - 1)) == 0, "sort space");
-static_assert(kSmpThreads == 4 * 256, "one thread per radix bin copy");
-static_assert(kSmpCand <= kSmpThreads && kSampleMaxLastN <= kSmpThreads && kSampleMaxTopK <= kSmpThreads, "one thread each");
 
 bool sample_rec_make(double temperature, int top_k, double top_p, double min_p, double repeat_penalty, int repeat_last_n,
                      double presence_penalty, double frequency_penalty, SampleRec& r, std::string& why) {
@@ -74,54 +66,14 @@ bool sample_rec_make(double temperature, int top_k, double top_p, double min_p, 
 namespace {
 
 struct SmpLds {
-    unsigned long long key[kSmpCand];  // gathered keys, sorted descending
+    SelLds sel;                        // the select's bins and the gathered keys, sorted descending
     unsigned long long red[kSmpWaves];
     double x[kSampleMaxTopK];          // candidate logits (/ temperature in the last softmax)
     double s[2][kSampleMaxTopK];       // scan ping-pong; s[cur][i] = inclusive prefix sum
     double dred[kSmpWaves];
     int32_t win[kSampleMaxLastN];
-    unsigned bins[4 * 256];            // radix bins, four copies each (lane & 3): equal digits collide less
-    unsigned hist[2][256];             // their sums, suffix-scan ping-pong
-    unsigned long long prefix;
-    unsigned need, n_ge, n_key;
     int idx;
 };
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// f(value, index) for every element of the row, each by one thread of the workgroup.  The
-// body of the row goes in 16-byte loads, kSmpUnroll of them in flight per thread before the
-// first is used (a row starts wherever slot * V puts it: the elements before the first
-// 16-byte boundary and after the last whole quad go singly).
-template <class F>
-__device__ __forceinline__ void for_row(const float* lg, int V, F f) {
-    const int t = threadIdx.x;
-    const int head = min(V, (int)(((16u - (unsigned)((uintptr_t)lg & 15u)) & 15u) >> 2));
-    const int n4 = (V - head) >> 2;
-    const float4* q = (const float4*)(lg + head);
-    if (t < head) f(lg[t], t);
-    for (int i0 = 0; i0 < n4; i0 += kSmpUnroll * kSmpThreads) {
-        float4 v[kSmpUnroll];
-#pragma unroll
-        for (int j = 0; j < kSmpUnroll; ++j) {
-            const int i = i0 + j * kSmpThreads + t;
-            if (i < n4) v[j] = q[i];
-        }
-#pragma unroll
-        for (int j = 0; j < kSmpUnroll; ++j) {
-            const int i = i0 + j * kSmpThreads + t;
-            if (i < n4) {
-                const int e = head + 4 * i;
-                f(v[j].x, e); f(v[j].y, e + 1); f(v[j].z, e + 2); f(v[j].w, e + 3);
-            }
-        }
-    }
-    const int e = head + 4 * n4 + t;
-    if (e < V) f(lg[e], e);
-}
 
 // softmax of L.x[0 .. n) (sorted descending: the max is x[0]) and its inclusive prefix sums
 // L.s[ret][0 .. n); returns the scan buffer.  Every thread calls it; `total` = the sum.
@@ -208,81 +160,21 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample(SampleArgs a) {
         __syncthreads();
         if (t == 0) {
             for (int w = 1; w < kSmpWaves; ++w) best = L.red[w] > best ? L.red[w] : best;
-            L.key[0] = best;
+            L.sel.key[0] = best;
         }
         __syncthreads();
-        chosen = L.key[0];
+        chosen = L.sel.key[0];
     } else {
         // ---- top_k: the elements whose key is >= a prefix, at most kSmpCand of them, into LDS ----
         const int k = min(R.top_k, V);
-        unsigned long long prefix = 0;
-        if (V > kSmpCand) {
-            unsigned need = (unsigned)k;  // candidates still to take from the elements matching the prefix
-            for (int shift = 56; shift >= 0; shift -= 8) {
-                L.bins[t] = 0;
-                __syncthreads();
-                for_row(lg, V, [&](float v, int i) {
-                    const unsigned long long key = argmax_key(v, i);
-                    if (shift == 56 || (key >> (shift + 8)) == (prefix >> (shift + 8)))
-                        atomicAdd(&L.bins[(((unsigned)(key >> shift) & 255u) << 2) | (unsigned)(lane & 3)], 1u);
-                });
-                __syncthreads();
-                if (t < 256) L.hist[0][t] = L.bins[4 * t] + L.bins[4 * t + 1] + L.bins[4 * t + 2] + L.bins[4 * t + 3];
-                __syncthreads();
-                // suffix sums: hist[cur][b] = elements in bins >= b
-                int cur = 0;
-                for (int o = 1; o < 256; o <<= 1) {
-                    if (t < 256) L.hist[cur ^ 1][t] = L.hist[cur][t] + (t + o < 256 ? L.hist[cur][t + o] : 0u);
-                    cur ^= 1;
-                    __syncthreads();
-                }
-                if (t < 256) {
-                    const unsigned ge = L.hist[cur][t], gt = t < 255 ? L.hist[cur][t + 1] : 0u;
-                    if (gt < need && need <= ge) {  // exactly one bin: the k-th largest key lies in it
-                        L.prefix = prefix | ((unsigned long long)t << shift);
-                        L.need = need - gt;
-                        L.n_ge = (unsigned)k - need + ge;  // elements with key >= the new prefix
-                    }
-                }
-                __syncthreads();
-                prefix = L.prefix;
-                need = L.need;
-                const unsigned n_ge = L.n_ge;
-                __syncthreads();
-                if (n_ge <= (unsigned)kSmpCand) break;  // at the last pass need == 1 and n_ge == k
-            }
-        }
-        if (t == 0) L.n_key = 0;
-        if (t < kSmpCand) L.key[t] = 0;
-        __syncthreads();
-        for_row(lg, V, [&](float v, int i) {
-            const unsigned long long key = argmax_key(v, i);
-            if (key >= prefix) {
-                const unsigned at = atomicAdd(&L.n_key, 1u);
-                if (at < (unsigned)kSmpCand) L.key[at] = key;
-            }
-        });
-        __syncthreads();
-        const int n_key = min((int)L.n_key, kSmpCand);
-        int n_sort = 64;
-        while (n_sort < n_key) n_sort <<= 1;
-        // bitonic sort, descending (the unused tail holds 0, below every key of a real logit)
-        for (int kk = 2; kk <= n_sort; kk <<= 1) {
-            for (int j = kk >> 1; j > 0; j >>= 1) {
-                const int p = t ^ j;
-                if (t < n_sort && p > t) {
-                    const unsigned long long x = L.key[t], y = L.key[p];
-                    const bool desc = (t & kk) == 0;
-                    if (desc ? x < y : x > y) { L.key[t] = y; L.key[p] = x; }
-                }
-                __syncthreads();
-            }
-        }
+        const auto nothing = [](float, int) {};
+        const unsigned long long prefix = V > kSmpCand ? select_prefix(L.sel, lg, V, k, nothing) : 0ull;
+        gather_sort(L.sel, lg, V, prefix, nothing);
         // ---- top_p, min_p, temperature, dist on the first k, FP64 ----
         int n = k;
         if (t < kSampleMaxTopK) {
             double x = 0.0;
-            const uint32_t id = 0xffffffffu - (uint32_t)(L.key[t] & 0xffffffffull);
+            const uint32_t id = 0xffffffffu - (uint32_t)(L.sel.key[t] & 0xffffffffull);
             if (t < n && id < (uint32_t)V) x = (double)lg[id];
             L.x[t] = x;
         }
@@ -309,13 +201,13 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample(SampleArgs a) {
         const int idx = pos - R.pos0;
         const double u = idx >= 0 && idx < R.n_uni ? R.uni[idx] : 0.0;
         const int pick = first_hit(L, n, t < n && L.s[cur][t] / total > u);
-        chosen = L.key[min(pick, n - 1)];
+        chosen = L.sel.key[min(pick, n - 1)];
         n_final = n;
     }
     if (a.cand) {
         if (t < n_final)
             a.cand[(size_t)slot * kSampleMaxTopK + t] =
-                (int32_t)(0xffffffffu - (uint32_t)((R.mode == SAMPLE_ARGMAX ? chosen : L.key[t]) & 0xffffffffull));
+                (int32_t)(0xffffffffu - (uint32_t)((R.mode == SAMPLE_ARGMAX ? chosen : L.sel.key[t]) & 0xffffffffull));
         if (t == 0) a.n_cand[slot] = n_final;
     }
     if (t < kArgSlots) st->key[pos & 1][t] = t == 0 ? chosen : 0ull;

@@ -335,6 +335,37 @@ def sample_logits(logits, history, params: Sequence, uniforms, want_penalized: b
     return ([int(t) for t in tok], [[int(c) for c in cand[i, :ncand[i]]] for i in range(rows)], pen, us.value)
 
 
+def logprob_rows(logits, history, params: Sequence, uniforms, n_top: Sequence[int], want_rows: bool = True):
+    """llmi_logprob_rows: k_logprob, k_sample, k_logprob_pick in step order over crafted rows.
+    logits, history, params, uniforms as sample_logits; n_top one of -1, 0..20 per row.
+    Returns a dict: tokens [rows], tok_logprob and lse float64 [rows] (NaN for a row with n_top
+    -1: the kernels left it alone), top_ids int32 and top_logprobs float64 [rows][20] (unused
+    entries -1 and -inf), rows the logits after the kernels (None unless wanted), usec the
+    event-timed microseconds of (k_logprob, k_sample, k_logprob_pick)."""
+    from ._lib import LOGPROBS_MAX_TOP
+
+    lg = np.ascontiguousarray(np.asarray(logits, dtype=np.float32))
+    rows, V = lg.shape
+    hist = np.ascontiguousarray(np.asarray(history, dtype=np.int32).reshape(rows, -1))
+    n_hist = hist.shape[1]
+    un = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64).reshape(rows))
+    nt = np.ascontiguousarray(np.asarray(n_top, dtype=np.int32).reshape(rows))
+    tok = np.zeros(rows, dtype=np.int32)
+    tok_lp, lse = np.full(rows, np.nan), np.full(rows, np.nan)
+    top_id = np.full((rows, LOGPROBS_MAX_TOP), -2, dtype=np.int32)
+    top_lp = np.full((rows, LOGPROBS_MAX_TOP), np.nan)
+    after = np.zeros((rows, V), dtype=np.float32) if want_rows else None
+    us = (C.c_double * 3)()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    r = lib().llmi_logprob_rows(vp(lg), rows, V, vp(hist) if n_hist else None, n_hist, sampler_params(params), vp(un),
+                                vp(nt), vp(tok), vp(tok_lp), vp(lse), vp(top_id), vp(top_lp),
+                                vp(after) if want_rows else None, C.cast(us, C.c_void_p))
+    if r != 0:
+        raise LlmiError(f"llmi_logprob_rows returned {r}: {last_error()}")
+    return {"tokens": [int(t) for t in tok], "tok_logprob": tok_lp, "lse": lse, "top_ids": top_id, "top_logprobs": top_lp,
+            "rows": after, "usec": tuple(us)}
+
+
 # the device's StepState (llmi_step_state) as a NumPy record
 STEP_STATE = np.dtype([("token_in", "<i4"), ("token_in_pos", "<i4"), ("pos_next", "<i4"), ("pos", "<i4"), ("token", "<i4"),
                        ("seq", "<u4"), ("key", "<u8", (2, 64))])
@@ -487,6 +518,41 @@ class Context:
         if r != n:
             raise LlmiError(f"llmi_generate_sampled_batch returned {r}: {last_error()}")
         return [list(out[i * n:(i + 1) * n]) for i in range(k)]
+
+    def generate_logprobs_batch(self, seqs: Sequence[int], first: Sequence[int], pos0: Sequence[int], n: int,
+                                params: Sequence, uniforms, n_top: Sequence[int]):
+        """llmi_generate_logprobs_batch: generate_sampled_batch that also returns, for each
+        sequence k with n_top[k] >= 0, the log-probabilities of its tokens under each step's raw
+        distribution and the n_top[k] most likely alternatives (sampling.token_logprobs on
+        the device).  Returns (tokens, logprobs): tokens as generate_sampled_batch; logprobs[k]
+        None for n_top[k] == -1, else a list of n entries (token_logprob, top_ids,
+        top_logprobs) with n_top[k] alternatives (fewer when the vocabulary is smaller)."""
+        from ._lib import LOGPROBS_MAX_TOP as T
+
+        k = len(seqs)
+        sa, fa, pa = (C.c_int32 * k)(*seqs), (C.c_int32 * k)(*first), (C.c_int32 * k)(*pos0)
+        na = (C.c_int32 * k)(*[int(t) for t in n_top])
+        un = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64).reshape(k, n))
+        out = (C.c_int32 * (k * n))()
+        tok_lp = np.full((k, n), np.nan)
+        top_id = np.full((k, n, T), -2, dtype=np.int32)
+        top_lp = np.full((k, n, T), np.nan)
+        r = lib().llmi_generate_logprobs_batch(self._h, k, sa, fa, pa, int(n), sampler_params(params),
+                                               un.ctypes.data_as(C.POINTER(C.c_double)), na, out,
+                                               tok_lp.ctypes.data_as(C.POINTER(C.c_double)),
+                                               top_id.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               top_lp.ctypes.data_as(C.POINTER(C.c_double)))
+        if r != n:
+            raise LlmiError(f"llmi_generate_logprobs_batch returned {r}: {last_error()}")
+        lps = []
+        for i in range(k):
+            if na[i] < 0:
+                lps.append(None)
+                continue
+            m = [int((top_id[i, j] >= 0).sum()) for j in range(n)]
+            lps.append([(float(tok_lp[i, j]), [int(t) for t in top_id[i, j, :m[j]]], [float(v) for v in top_lp[i, j, :m[j]]])
+                        for j in range(n)])
+        return [list(out[i * n:(i + 1) * n]) for i in range(k)], lps
 
     def seq_rm(self, seq: int, p0: int = 0, p1: int = -1) -> bool:
         """llama_kv_self_seq_rm (tail removal)."""

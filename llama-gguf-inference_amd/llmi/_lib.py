@@ -138,6 +138,7 @@ class llmi_sampler_params(C.Structure):
 
 
 SAMPLE_MAX_TOP_K, SAMPLE_MAX_LAST_N = 256, 256  # LLMI_SAMPLE_MAX_*
+LOGPROBS_MAX_TOP = 20  # LLMI_LOGPROBS_MAX_TOP
 
 # name -> (restype, argtypes); every entry point declared in include/llmi.h
 _P = C.c_void_p
@@ -187,6 +188,12 @@ SIGNATURES = {
     "llmi_generate_sampled_batch": (C.c_int32, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                 C.POINTER(C.c_int32), C.c_int32, C.POINTER(llmi_sampler_params),
                                                 C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "llmi_generate_logprobs_batch": (C.c_int32, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_int32), C.c_int32, C.POINTER(llmi_sampler_params),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "llmi_logprob_rows": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(llmi_sampler_params), _P, _P, _P,
+                                      _P, _P, _P, _P, _P, _P]),
     "llmi_sample_logits": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(llmi_sampler_params), _P, _P, _P,
                                        _P, _P, C.POINTER(C.c_double)]),
     "llama_kv_self_seq_rm": (C.c_bool, [_P, C.c_int32, C.c_int32, C.c_int32]),

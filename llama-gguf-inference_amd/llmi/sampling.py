@@ -33,7 +33,9 @@ random() double and searches it in the normalised cdf), so a sampled request wit
 device limits (device_eligible) decodes on the device as well: the host draws the chunk's
 uniforms from the request's generator and llmi_generate_sampled_batch runs this chain on
 the device logits (csrc/sample.hip), the same seed giving the same tokens as the host
-path; other requests are sampled here over copied logits.  The random stream is
+path; other requests are sampled here over copied logits.  token_logprobs is the host
+definition of what a request for logprobs gets (the raw distribution, before this chain), which
+llmi_generate_logprobs_batch restates on the device (csrc/logprob.hip).  The random stream is
 numpy's PCG64, not llama.cpp's mt19937: sampled text with a given seed is reproducible
 here but not token-identical to llama-server's (parity of sampled output is unpinned;
 greedy output is the parity bar, tests/test_gpu_*.py).
@@ -131,6 +133,36 @@ def penalized_logits(p: SamplingParams, logits: np.ndarray, history: Sequence[in
             v = v - counts * p.frequency_penalty - (counts > 0) * p.presence_penalty
             lg[toks] = v.astype(np.float32)
     return lg
+
+
+def token_logprobs(logits: np.ndarray, n_top: int):
+    """(lse, ids, logprobs) of one raw float32 logits row: no penalties and no temperature,
+    what llama-server reports with post_sampling_probs off.  This is the definition the
+    device restates (csrc/logprob.hip).
+
+      x = logits.astype(float64), m = x.max(), lse = m + log(sum(exp(x - m)))
+      logprobs[t] = x[t] - lse for EVERY token t (a float64 array of the row's length) --
+      never log(p): a token more than 745 below the maximum keeps a finite value
+      ids = the top min(n_top, V) token ids in argmax_key order, logit descending and the
+      lower id first on ties (np.lexsort((ids, -logits)), sample_trace's ordering)
+
+    -inf entries are legal and yield -inf.  A row with a NaN, or whose maximum is not finite,
+    is outside the definition: nothing is promised for it, here or on the device."""
+    x = np.asarray(logits, dtype=np.float32).astype(np.float64)
+    m = x.max()
+    lse = float(m + np.log(np.sum(np.exp(x - m))))
+    k = max(0, min(int(n_top), x.size))
+    if k == 0:
+        ids = np.zeros(0, dtype=np.int64)
+    elif k < x.size:
+        # the k largest; of a run of equal logits that straddles the k-th place, the lower ids
+        kth = x[np.argpartition(-x, k - 1)[k - 1]]
+        above = np.flatnonzero(x > kth)
+        ids = np.concatenate([above, np.flatnonzero(x == kth)[:k - above.size]])
+    else:
+        ids = np.arange(x.size)
+    ids = ids[np.lexsort((ids, -x[ids]))]
+    return lse, ids, x - lse
 
 
 def sample_trace(p: SamplingParams, logits: np.ndarray, history: Sequence[int], u: Optional[float]) -> SampleTrace:

@@ -24,7 +24,26 @@ Sampling follows llama-server (llmi/sampling.py): temperature / top_k / top_p / 
 repeat, presence and frequency penalties / seed per request, llama-server's defaults
 (temperature 0.8, top_k 40, top_p 0.95, min_p 0.05) or the --temp / --top-k / ... flags;
 `stop` strings end the generation (the text stops before them); `ignore_eos` and
-`n_predict` follow llama-server; `n` > 1 and `logprobs` are rejected with a 400.
+`n_predict` follow llama-server; `n` > 1 is rejected with a 400.
+
+Log-probabilities are opt-in: `--max-logprobs N` (LLMI_MAX_LOGPROBS; default 0, at most 20).
+With the default every request for them gets a 400, as before; with N > 0
+
+  POST /v1/chat/completions    logprobs: true, top_logprobs: 0..N -> choices[0].logprobs.content =
+                               [{token, logprob, bytes, top_logprobs: [{token, logprob, bytes}]}]
+  POST /v1/completions         logprobs: k -> choices[0].logprobs = {tokens, token_logprobs,
+                               top_logprobs: [{text: logprob}], text_offset}
+  POST /completion             n_probs: k -> completion_probabilities: [{id, token, bytes, logprob,
+                               top_logprobs: [{id, token, bytes, logprob}]}]
+
+report each generated token's log-probability under the raw distribution (no penalties, no
+temperature: llama-server's post_sampling_probs off; llmi/sampling.py token_logprobs) and the
+k most likely alternatives; non-finite values are written as -9999.0.  Streamed chunks carry
+the entries of the tokens consumed since the previous chunk, and entries end where a stop
+string cuts the text.  Requests decoded on the device get them from the device
+(llmi_generate_logprobs_batch, still one batched call per step and no logits copy); a
+request's first token, requests on the host sampler path, and all of them with
+LLMI_DEVICE_SAMPLING=0, from the copied logits.
 Greedy requests (temperature 0 or top_k 1, no penalties) decode on the device with
 on-device argmax feedback.  Sampled requests within the device sampler's limits (top_k
 1..256, a penalty window of at most 256 tokens) join them in the same batched call: the
@@ -56,12 +75,20 @@ from typing import Callable, Iterable, Optional
 
 import numpy as np
 
-from .sampling import Sampler, SamplingParams, StopFilter, device_eligible, find_stop, parse_stop
+from .sampling import Sampler, SamplingParams, StopFilter, device_eligible, find_stop, parse_stop, token_logprobs
 
 # a greedy slot of a sampled batched call: the chain that is an argmax of the raw logits
 _GREEDY = SamplingParams(temperature=0.0, top_k=1, top_p=1.0, min_p=0.0)
 
 VERSION = "llmi-server 0.1 (libllmi, gfx950)"
+MAX_LOGPROBS = 20     # llmi.h LLMI_LOGPROBS_MAX_TOP: the most --max-logprobs can allow
+LOGPROB_FLOOR = -9999.0  # what JSON carries for a non-finite log-probability (OpenAI's documented floor)
+
+
+def host_logprob_entry(logits: np.ndarray, token: int, n_top: int) -> tuple:
+    """A token's entry (logprob, alternative ids, their logprobs) from a copied logits row."""
+    _, ids, lp = token_logprobs(logits, n_top)
+    return float(lp[token]), [int(i) for i in ids], [float(lp[i]) for i in ids]
 
 
 # --------------------------------------------------------------------------------------
@@ -194,11 +221,15 @@ class Request:
     """One generation: prompt ids in, token lists out through `q` (None terminates).
     `sampling` None or greedy: device argmax; else a Sampler: its chain runs on the device
     fed by its generator's uniforms, or on the host over each step's logits (Replica._step).
-    `stop`: strings that end the generation (checked on the detokenized output)."""
+    `stop`: strings that end the generation (checked on the detokenized output).
+    `n_top` >= 0: every token comes with its log-probability entry (host_logprob_entry's
+    shape) in `lp`, parallel to `out`."""
 
     def __init__(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
-                 sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None):
+                 sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None, n_top: int = -1):
         self.prompt, self.max_tokens, self.ignore_eos = list(prompt), max_tokens, ignore_eos
+        self.n_top = n_top
+        self.lp: list[tuple] = []
         self.sampler = Sampler(sampling) if sampling is not None and not sampling.greedy else None
         self.stop = list(stop or [])
         self.out: list[int] = []
@@ -213,11 +244,13 @@ class Request:
         self.last = -1
         self.pos = 0
 
-    def emit(self, toks: list[int]) -> None:
+    def emit(self, toks: list[int], entries: Optional[list[tuple]] = None) -> None:
         if toks:
             if self.t_first is None:
                 self.t_first = time.perf_counter()
             self.out += toks
+            if self.n_top >= 0:  # before the tokens are announced: a reader of q finds them in lp
+                self.lp += entries[:len(toks)]
             self.q.put(list(toks))
 
     def done(self, finish: str) -> None:
@@ -252,6 +285,8 @@ class Replica:
         self.stop = False
         # device sampling: the context has the call, and LLMI_DEVICE_SAMPLING is not 0
         self.device_sampling = hasattr(ctx, "generate_sampled_batch") and os.environ.get("LLMI_DEVICE_SAMPLING", "1") != "0"
+        # device log-probabilities: the same, and the context has that call too
+        self.device_logprobs = self.device_sampling and hasattr(ctx, "generate_logprobs_batch")
         self.th = threading.Thread(target=self._run, name=f"llmi-replica-{idx}", daemon=True)
         self.th.start()
 
@@ -296,8 +331,10 @@ class Replica:
             if rc != 0:
                 raise RuntimeError(f"llama_decode returned {rc}")
             first = c.greedy(-1) if r.sampler is None else r.sampler.sample(c.logits(-1), r.prompt)
+            # the first token's entry: from the prompt's logits on the host, on every path
+            entries = [host_logprob_entry(c.logits(-1), first, r.n_top)] if r.n_top >= 0 else None
             r.seq, r.pos = seq, len(r.prompt)
-            if self._take(r, [first]):
+            if self._take(r, [first], entries):
                 self.free.append(seq)
             else:
                 r.last = first
@@ -306,19 +343,20 @@ class Replica:
             self.free.append(seq)
             r.fail(str(e))
 
-    def _take(self, r: Request, toks: list[int]) -> bool:
-        """Emit generated tokens up to EOS / max_tokens; True when the request is done."""
+    def _take(self, r: Request, toks: list[int], entries: Optional[list[tuple]] = None) -> bool:
+        """Emit generated tokens (with their logprob entries, toks' parallel) up to EOS /
+        max_tokens; True when the request is done."""
         emit = []
         for t in toks:
             if t in self.eog and not r.ignore_eos:
-                r.emit(emit)
+                r.emit(emit, entries)
                 self.tokens += len(emit)
                 r.done("stop")
                 return True
             emit.append(t)
             if len(r.out) + len(emit) >= r.max_tokens:
                 break
-        r.emit(emit)
+        r.emit(emit, entries)
         self.tokens += len(emit)
         if r.stop and self.detok is not None and emit and self._stop_seen(r, len(emit)):
             r.done("stop")
@@ -344,28 +382,46 @@ class Replica:
             k = min(k, 4)  # stop strings are checked between decode calls
         c = self.ctx
         t0 = time.perf_counter()
-        greedy = [r for r in batch if r.sampler is None]
-        ondev = [r for r in batch if r.sampler is not None and self.device_sampling and device_eligible(r.sampler.p)]
-        sampled = [r for r in batch if r.sampler is not None and r not in ondev]
+        # a request that wants log-probabilities where the device cannot give them (no such
+        # call on this context, LLMI_DEVICE_SAMPLING=0, a chain outside the device limits)
+        # takes the host path below, greedy ones included: its entries come from copied logits
+        hostlp = [r for r in batch if r.n_top >= 0 and not (
+            self.device_logprobs and (r.sampler is None or device_eligible(r.sampler.p)))]
+        greedy = [r for r in batch if r.sampler is None and r not in hostlp]
+        ondev = [r for r in batch if r.sampler is not None and self.device_sampling and device_eligible(r.sampler.p)
+                 and r not in hostlp]
+        sampled = [r for r in batch if r not in greedy and r not in ondev]
         outs: dict[int, list[int]] = {}
-        if ondev:
+        lps: dict[int, list[tuple]] = {}
+        want_lp = any(r.n_top >= 0 for r in greedy + ondev)
+        if ondev or want_lp:
             # sampled requests within the device sampler's limits and the greedy ones advance
             # k tokens in one call (one weight pass per step for all of them): each sampled
             # request's chain runs on the device logits, fed the next k draws of its own
             # generator -- the draws the host path would make, so a seed gives the same text
-            # on either path (draws past a request's end are discarded with it)
+            # on either path (draws past a request's end are discarded with it).  If any of
+            # them wants log-probabilities the call is the one that computes them next to the
+            # sampler, with -1 for the others: still one call and one weight pass
             group = greedy + ondev
             params = [_GREEDY] * len(greedy) + [r.sampler.p for r in ondev]
             unis = [np.zeros(k)] * len(greedy) + [r.sampler.rng.random(k) if r.sampler.p.temperature > 0.0 else np.zeros(k)
                                                   for r in ondev]
+
+            def call(rs, ps, us):
+                seqs, last, pos = [r.seq for r in rs], [r.last for r in rs], [r.pos for r in rs]
+                if want_lp:
+                    return c.generate_logprobs_batch(seqs, last, pos, k, ps, us, [r.n_top for r in rs])
+                return c.generate_sampled_batch(seqs, last, pos, k, ps, us), [None] * len(rs)
+
             try:
-                got = c.generate_sampled_batch([r.seq for r in group], [r.last for r in group], [r.pos for r in group],
-                                               k, params, unis)
+                got, ent = call(group, params, unis)
             except Exception:  # not batchable here: one sequence at a time, same results
-                got = [c.generate_sampled_batch([r.seq], [r.last], [r.pos], k, [p], [u])[0]
-                       for r, p, u in zip(group, params, unis)]
-            for r, toks in zip(group, got):
+                one = [call([r], [p], [u]) for r, p, u in zip(group, params, unis)]
+                got, ent = [o[0][0] for o in one], [o[1][0] for o in one]
+            for r, toks, e in zip(group, got, ent):
                 outs[id(r)] = toks
+                if e is not None:
+                    lps[id(r)] = e
         elif greedy:
             # greedy slots decode k tokens per call with the argmax fed back on the device,
             # whether or not sampled requests share the replica
@@ -386,7 +442,12 @@ class Replica:
             if rc != 0:
                 raise RuntimeError(f"llama_decode returned {rc}")
             for i, r in enumerate(sampled):
-                outs[id(r)] = [r.sampler.sample(c.logits(i), r.prompt + r.out)]
+                lg = c.logits(i)
+                # (a greedy request is here for its entries only: first max wins, as on the device)
+                tok = int(np.argmax(lg)) if r.sampler is None else r.sampler.sample(lg, r.prompt + r.out)
+                outs[id(r)] = [tok]
+                if r.n_top >= 0:
+                    lps[id(r)] = [host_logprob_entry(lg, tok, r.n_top)]
         self.busy_s += time.perf_counter() - t0
         self._stats()
         done = []
@@ -394,7 +455,7 @@ class Replica:
             toks = outs[id(r)]
             r.pos += len(toks)
             r.last = toks[-1]
-            if self._take(r, toks):
+            if self._take(r, toks, lps.get(id(r))):
                 done.append(r)
         for r in done:
             self.active.remove(r)
@@ -428,8 +489,11 @@ class Engine:
     ties to the lowest index) and are served there with continuous batching."""
 
     def __init__(self, path: str, n_ctx: int, n_gpu_layers: int, devices: list[int], slots: int = 4,
-                 chunk: int = 8, contexts=None, sampling: Optional[SamplingParams] = None, numerics: int = 0):
+                 chunk: int = 8, contexts=None, sampling: Optional[SamplingParams] = None, numerics: int = 0,
+                 max_logprobs: int = 0):
         self.path, self.n_ctx, self.ngl, self.devices = path, n_ctx, n_gpu_layers, devices
+        # alternatives a request may ask for (--max-logprobs); 0: logprobs are refused with a 400
+        self.max_logprobs = max(0, min(int(max_logprobs), MAX_LOGPROBS))
         self.numerics = numerics  # llmi.NUMERICS_GENERIC / NUMERICS_X86 (DESIGN.md §5)
         self.sampling = sampling or SamplingParams()  # server defaults (llama-server's)
         self.slots, self.chunk = max(1, slots), max(1, chunk)
@@ -479,8 +543,8 @@ class Engine:
             self.error = str(e)
 
     def submit(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
-               sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None) -> Request:
-        r = Request(prompt, max_tokens, ignore_eos, sampling, stop)
+               sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None, n_top: int = -1) -> Request:
+        r = Request(prompt, max_tokens, ignore_eos, sampling, stop, n_top)
         rep = min(self.replicas, key=lambda x: (x.load(), x.idx))
         rep.submit(r)
         return r
@@ -488,15 +552,27 @@ class Engine:
     def generate(self, prompt: list[int], max_tokens: int, ignore_eos: bool, on_tokens: Callable[[list[int]], None],
                  chunk: int = 8, sampling: Optional[SamplingParams] = None,
                  stop: Optional[list[str]] = None) -> tuple[list[int], str]:
-        r = self.submit(prompt, max_tokens, ignore_eos, sampling, stop)
+        ids, finish, _ = self.generate_logprobs(prompt, max_tokens, ignore_eos, lambda toks, _e: on_tokens(toks), chunk,
+                                                sampling, stop, -1)
+        return ids, finish
+
+    def generate_logprobs(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
+                          on_tokens: Callable[[list[int], Optional[list[tuple]]], None], chunk: int = 8,
+                          sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None,
+                          n_top: int = -1) -> tuple[list[int], str, list[tuple]]:
+        """generate with each token's logprob entry (n_top >= 0; else None) handed to
+        on_tokens along with the tokens; returns (tokens, finish, entries)."""
+        r = self.submit(prompt, max_tokens, ignore_eos, sampling, stop, n_top)
+        seen = 0
         while True:
             toks = r.q.get()
             if toks is None:
                 break
-            on_tokens(toks)
+            on_tokens(toks, r.lp[seen:seen + len(toks)] if n_top >= 0 else None)
+            seen += len(toks)
         if r.error:
             raise RuntimeError(r.error)
-        return r.out, r.finish or "length"
+        return r.out, r.finish or "length", r.lp
 
     def health(self) -> dict:
         """Per-replica serving metrics for /health (kept well under the gateway's 4 KB read,
@@ -554,6 +630,66 @@ class Handler(BaseHTTPRequestHandler):
             return json.loads(raw or b"{}")
         except json.JSONDecodeError:
             return None
+
+    @staticmethod
+    def _logprobs_wanted(req: dict, route: str, limit: int) -> int:
+        """The alternatives a request asks for with its route's fields (-1: no logprobs);
+        ValueError for what the route or the server's --max-logprobs does not take."""
+        def count(name):
+            v = req.get(name)
+            if v is None:
+                return None
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"'{name}' must be a non-negative integer")
+            return v
+
+        n = -1
+        if route == "/v1/chat/completions":
+            lp = req.get("logprobs")
+            if lp == 0 and lp is not None:
+                lp = False  # (0 has always been taken for false here)
+            if lp not in (None, False) and lp is not True:
+                raise ValueError("'logprobs' must be a boolean")
+            top = count("top_logprobs")
+            if top is not None and not lp:
+                raise ValueError("'top_logprobs' requires 'logprobs' to be true")
+            if lp:
+                n = top or 0
+        else:
+            if req.get("top_logprobs") not in (None, 0):
+                raise ValueError("'top_logprobs' belongs to /v1/chat/completions; this route takes 'logprobs': k")
+            lp = req.get("logprobs")
+            k = None if lp is False else 0 if lp is True else count("logprobs")
+            if route == "/completion" and count("n_probs"):
+                k = max(k or 0, count("n_probs"))
+            if k is not None and (k > 0 or lp is True or limit > 0):
+                n = k  # (logprobs: 0 on a server without --max-logprobs stays what it was: nothing)
+        if n >= 0 and limit <= 0:
+            raise ValueError("logprobs are not supported (the server runs without --max-logprobs)")
+        if n > limit:
+            raise ValueError(f"at most {limit} top logprobs are served (--max-logprobs {limit})")
+        return n
+
+    def _logprob_json(self, route: str, ids: list[int], entries: list[tuple], starts: list[int]) -> dict:
+        """The route's response fields for tokens `ids` with their entries and text offsets."""
+        v = self.engine.vocab
+        fin = lambda x: float(x) if np.isfinite(x) else LOGPROB_FLOOR  # noqa: E731
+        text = lambda t: v.detokenize([t])  # noqa: E731
+        raw = lambda t: list(text(t).encode("utf-8"))  # noqa: E731
+        if route == "/v1/chat/completions":
+            return {"logprobs": {"content": [
+                {"token": text(t), "logprob": fin(lp), "bytes": raw(t),
+                 "top_logprobs": [{"token": text(a), "logprob": fin(x), "bytes": raw(a)} for a, x in zip(alt, alp)]}
+                for t, (lp, alt, alp) in zip(ids, entries)]}}
+        out = {"logprobs": {"tokens": [text(t) for t in ids], "token_logprobs": [fin(e[0]) for e in entries],
+                            "top_logprobs": [{text(a): fin(x) for a, x in zip(alt, alp)} for _, alt, alp in entries],
+                            "text_offset": list(starts)}}
+        if route == "/completion":
+            out["completion_probabilities"] = [
+                {"id": t, "token": text(t), "bytes": raw(t), "logprob": fin(lp),
+                 "top_logprobs": [{"id": a, "token": text(a), "bytes": raw(a), "logprob": fin(x)} for a, x in zip(alt, alp)]}
+                for t, (lp, alt, alp) in zip(ids, entries)]
+        return out
 
     # ---- routes
     def do_GET(self):
@@ -616,8 +752,7 @@ class Handler(BaseHTTPRequestHandler):
                 max_tokens = eng.n_ctx
             if int(req.get("n", 1)) != 1:
                 raise ValueError("only n = 1 is supported")
-            if req.get("logprobs") not in (None, False, 0) or req.get("top_logprobs") not in (None, 0):
-                raise ValueError("logprobs are not supported")
+            n_top = self._logprobs_wanted(req, route, getattr(eng, "max_logprobs", 0))
             sampling = getattr(eng, "sampling", SamplingParams()).with_request(req)
             stop = parse_stop(req.get("stop"))
         except (ValueError, TypeError) as e:
@@ -628,9 +763,14 @@ class Handler(BaseHTTPRequestHandler):
         created = int(time.time())
         obj = "chat.completion" if chat else "text_completion"
         if not stream:
+            entries = None
             try:
-                ids, finish = eng.generate(prompt, max_tokens, ignore_eos, lambda _t: None, chunk=32,
-                                           sampling=sampling, stop=stop)
+                if n_top >= 0:
+                    ids, finish, entries = eng.generate_logprobs(prompt, max_tokens, ignore_eos, lambda _t, _e: None,
+                                                                 chunk=32, sampling=sampling, stop=stop, n_top=n_top)
+                else:
+                    ids, finish = eng.generate(prompt, max_tokens, ignore_eos, lambda _t: None, chunk=32,
+                                               sampling=sampling, stop=stop)
             except Exception as e:  # a failed llama_decode: OpenAI-shaped 500, not a dropped socket
                 return self._send_json(500, _error(500, str(e), "server_error"))
             text = v.detokenize(ids)
@@ -639,11 +779,23 @@ class Handler(BaseHTTPRequestHandler):
                 text, finish = text[:cut], "stop"
             choice = ({"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": finish}
                       if chat else {"index": 0, "text": text, "logprobs": None, "finish_reason": finish})
+            extra = {}
+            if entries is not None:
+                # where each token's text begins (the streaming decoder's offsets); the entries
+                # end with the last token that begins before a stop string's cut
+                sd, starts, at = v.stream(), [], 0
+                for t in ids:
+                    starts.append(at)
+                    at += len(sd.push(t))
+                keep = len(ids) if cut is None else sum(1 for b in starts if b < cut)
+                lj = self._logprob_json(route, ids[:keep], entries[:keep], starts[:keep])
+                choice["logprobs"] = lj.pop("logprobs")
+                extra = lj
             return self._send_json(200, {
                 "id": rid, "object": obj, "created": created, "model": eng.model_id, "choices": [choice],
                 "usage": {"prompt_tokens": len(prompt), "completion_tokens": len(ids),
                           "total_tokens": len(prompt) + len(ids)},
-                "llmi": {"tokens": ids}})
+                "llmi": {"tokens": ids}, **extra})
         # SSE: headers, one data: line per token batch, final chunk, [DONE], close
         self.send_response(200)
         self.send_header("Content-Type", "text/event-stream")
@@ -664,24 +816,42 @@ class Handler(BaseHTTPRequestHandler):
         sd = v.stream()
         sf = StopFilter(stop)
 
-        def on_tokens(ts: list[int]) -> None:
-            for t in ts:
+        held: list[tuple] = []  # (token, entry, text offset) consumed since the last sent chunk
+
+        def chunk_of(piece: str) -> None:
+            ch = ({"index": 0, "delta": {"content": piece}, "finish_reason": None} if chat
+                  else {"index": 0, "text": piece, "logprobs": None, "finish_reason": None})
+            extra = {}
+            if n_top >= 0:
+                # the entries travel with the chunk that releases their text; those whose text
+                # begins at or after a stop string's cut (sf.sent once stopped) are dropped
+                live = [h for h in held if not sf.stopped or h[2] < sf.sent]
+                lj = self._logprob_json(route, [h[0] for h in live], [h[1] for h in live], [h[2] for h in live])
+                ch["logprobs"] = lj.pop("logprobs")
+                extra = lj
+                held.clear()
+            event({"id": rid, "object": cobj, "created": created, "model": eng.model_id, "choices": [ch], **extra})
+
+        def on_tokens(ts: list[int], entries=None) -> None:
+            for i, t in enumerate(ts):
+                if n_top >= 0 and not sf.stopped:
+                    held.append((t, entries[i], len(sf.text)))
                 piece = sf.push(sd.push(t))
                 if not piece:
                     continue  # an incomplete UTF-8 sequence, or a possible stop-string prefix: held back
-                ch = ({"index": 0, "delta": {"content": piece}, "finish_reason": None} if chat
-                      else {"index": 0, "text": piece, "logprobs": None, "finish_reason": None})
-                event({"id": rid, "object": cobj, "created": created, "model": eng.model_id, "choices": [ch]})
+                chunk_of(piece)
 
         try:
-            ids, finish = eng.generate(prompt, max_tokens, ignore_eos, on_tokens, chunk=4, sampling=sampling, stop=stop)
+            if n_top >= 0:
+                ids, finish, _ = eng.generate_logprobs(prompt, max_tokens, ignore_eos, on_tokens, chunk=4,
+                                                       sampling=sampling, stop=stop, n_top=n_top)
+            else:
+                ids, finish = eng.generate(prompt, max_tokens, ignore_eos, on_tokens, chunk=4, sampling=sampling, stop=stop)
             tail = sf.push(sd.flush()) + sf.flush()
             if sf.stopped:
                 finish = "stop"
-            if tail:
-                ch = ({"index": 0, "delta": {"content": tail}, "finish_reason": None} if chat
-                      else {"index": 0, "text": tail, "logprobs": None, "finish_reason": None})
-                event({"id": rid, "object": cobj, "created": created, "model": eng.model_id, "choices": [ch]})
+            if tail or any(not sf.stopped or h[2] < sf.sent for h in held):
+                chunk_of(tail)
             last = ({"index": 0, "delta": {}, "finish_reason": finish} if chat
                     else {"index": 0, "text": "", "logprobs": None, "finish_reason": finish})
             event({"id": rid, "object": cobj, "created": created, "model": eng.model_id, "choices": [last],
@@ -721,6 +891,9 @@ def parse_args(argv=None):
     ap.add_argument("-np", "--parallel", type=int, default=int(os.environ.get("LLMI_SLOTS", "4")),
                     help="sequences (slots) per replica decoded together (continuous batching)")
     ap.add_argument("--decode-chunk", type=int, default=8, help="tokens per batched decode call")
+    ap.add_argument("--max-logprobs", type=int, default=int(os.environ.get("LLMI_MAX_LOGPROBS", "0")),
+                    help=f"most top_logprobs / logprobs / n_probs a request may ask for, at most {MAX_LOGPROBS} "
+                         "(0, the default: requests for logprobs get a 400)")
     ap.add_argument("--numerics", choices=NUMERICS_CHOICES, default=None,
                     help="fp32 association of every kernel: ggml's generic order, or the oracle's model of "
                          "upstream's x86 AVX2 association (non-repack); '-fa': decode attention in ggml's CPU "
@@ -771,7 +944,8 @@ def main(argv=None) -> int:
                         repeat_penalty=args.repeat_penalty, repeat_last_n=args.repeat_last_n,
                         presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty, seed=args.seed)
     eng = Engine(args.model, args.ctx_size, args.ngl, list(range(max(1, args.replicas))), slots=args.parallel,
-                 chunk=args.decode_chunk, sampling=sp, numerics=numerics_value(args.numerics))
+                 chunk=args.decode_chunk, sampling=sp, numerics=numerics_value(args.numerics),
+                 max_logprobs=args.max_logprobs)
     srv = make_server(eng, args.host, args.port, key)
     threading.Thread(target=eng.load, daemon=True).start()
     print(f"[llmi-server] listening on {args.host}:{args.port}", file=sys.stderr, flush=True)
