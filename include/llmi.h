@@ -166,6 +166,16 @@ void llama_kv_self_clear(struct llama_context* ctx);
  * prompt-cache truncation): remove positions [p0, p1) of seq_id (-1: every sequence).
  * Only tail removal (p1 < 0) is supported; p0 <= 0 clears the sequence. */
 bool llama_kv_self_seq_rm(struct llama_context* ctx, llama_seq_id seq_id, llama_pos p0, llama_pos p1);
+/* upstream llama_kv_self_seq_cp / llama_memory_seq_cp (the server's prompt cache: a prefix
+ * another slot holds): copy positions [p0, p1) of seq_src into seq_dst on the device, K, V
+ * and token history bit for bit, in one launch (k_kv_seq_cp).  p0 <= 0: 0; p1 < 0: seq_src's
+ * past.  Afterwards seq_dst holds its own [0, p0), seq_src's [p0, p1), and its past is p1
+ * (a copy of no positions sets it to p0); its decode state is left as a tail removal leaves
+ * it, so decoding from p1 on gives the bits seq_src would give.  Synchronises before it
+ * returns.  false, llmi_last_error() naming the argument and nothing changed: a null
+ * context, a sequence outside 0..n_seq_max-1, seq_src == seq_dst, p1 beyond seq_src's past,
+ * p0 beyond seq_dst's past (a hole), p0 >= p1 > 0. */
+bool llama_kv_self_seq_cp(struct llama_context* ctx, llama_seq_id seq_src, llama_seq_id seq_dst, llama_pos p0, llama_pos p1);
 /* upstream llama_memory_seq_pos_max: last position held by seq_id, -1 if empty */
 int32_t llmi_seq_pos_max(const struct llama_context* ctx, llama_seq_id seq_id);
 
@@ -524,6 +534,16 @@ double llmi_bench_stream(const void* dev, int32_t n_bufs, uint64_t stride, uint6
  * [n_head*head_dim].  n_ctx a multiple of 256.  0 on success. */
 int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t n_kv, int32_t n_ctx, const float* q,
                        const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode);
+/* k_kv_seq_cp alone (llama_kv_self_seq_cp's launch) over device pointers, on the null
+ * stream, synchronised: positions [p0, p1) of the src caches and history into the dst ones.
+ * K [n_planes][n_ctx][head_dim] f16, V transposed [n_planes][head_dim][n_ctx] f16 (n_planes =
+ * n_layer * n_head_kv), hist [n_ctx] int32.  usec (optional): the launch's event-timed device
+ * microseconds.  < 0 before any device call, llmi_last_error() naming the argument: a null
+ * pointer, n_planes <= 0, head_dim no positive multiple of 8, n_ctx no positive multiple of
+ * 256, anything other than 0 <= p0 < p1 <= n_ctx.  0 on success. */
+int32_t llmi_kv_seq_copy(int32_t n_planes, int32_t head_dim, int32_t n_ctx, int32_t p0, int32_t p1,
+                         const uint16_t* kc_src, const uint16_t* vc_src, const int32_t* hist_src,
+                         uint16_t* kc_dst, uint16_t* vc_dst, int32_t* hist_dst, double* usec);
 /* The path launch_attention takes for this head shape at the KV bound kv_bound (a multiple
  * of 256 in the engine) under `mode` (0 auto, 1..7 forced, LLMI_ATTN_MODE's numbering): 1
  * fused, 2 split, 3 two-kernel, 4 exchange, 5 register-prefetched, 6 dim-split, 7

@@ -612,6 +612,49 @@ bool llama_kv_self_seq_rm(struct llama_context* ctx, llama_seq_id seq_id, llama_
     return true;
 }
 
+bool llama_kv_self_seq_cp(struct llama_context* ctx, llama_seq_id seq_src, llama_seq_id seq_dst, llama_pos p0, llama_pos p1) {
+    API_TRY
+    const std::string who = "llama_kv_self_seq_cp: ";
+    if (!ctx) { set_err(who + "ctx is a null pointer"); return false; }
+    Context& c = ctx->c;
+    if (seq_src < 0 || seq_src >= c.n_seq) { set_err(who + "seq_src out of range (n_seq_max)"); return false; }
+    if (seq_dst < 0 || seq_dst >= c.n_seq) { set_err(who + "seq_dst out of range (n_seq_max)"); return false; }
+    if (seq_src == seq_dst) { set_err(who + "seq_src and seq_dst are the same sequence"); return false; }
+    const int past_src = seq_past_of(c, seq_src), past_dst = seq_past_of(c, seq_dst);
+    if (p0 < 0) p0 = 0;
+    if (p1 < 0) p1 = past_src;
+    if (p1 > past_src) { set_err(who + "p1 beyond seq_src's past"); return false; }
+    if (p0 > past_dst) { set_err(who + "p0 beyond seq_dst's past (would leave a hole)"); return false; }
+    if (p1 > 0 && p0 >= p1) { set_err(who + "p0 >= p1: an empty range"); return false; }
+    if (p1 <= 0) {  // nothing to copy: seq_dst keeps its own [0, p0)
+        set_seq_past(c, seq_dst, p0);
+        return true;
+    }
+    const HParams& hp = c.m->hp;
+    KvCopyArgs a;
+    a.kc_src = c.kc0 + (size_t)seq_src * c.kv_seq_elems;
+    a.vc_src = c.vc0 + (size_t)seq_src * c.kv_seq_elems;
+    a.hist_src = c.hist0 + (size_t)seq_src * c.n_ctx;
+    a.kc_dst = c.kc0 + (size_t)seq_dst * c.kv_seq_elems;
+    a.vc_dst = c.vc0 + (size_t)seq_dst * c.kv_seq_elems;
+    a.hist_dst = c.hist0 + (size_t)seq_dst * c.n_ctx;
+    a.n_planes = hp.n_layer * hp.n_head_kv;
+    a.head_dim = hp.head_dim;
+    a.n_ctx = c.n_ctx;
+    a.p0 = p0;
+    a.p1 = p1;
+    if (!kv_seq_cp_ok(a)) { set_err(who + "unsupported cache shape"); return false; }
+    (void)hipSetDevice(c.device);
+    (void)hipGetLastError();
+    hipError_t e = launch_kv_seq_cp(a, c.max_blocks, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) { set_err(who + hip_err(e)); return false; }
+    // seq_dst's StepState stays: the next call sets token and position from the host
+    set_seq_past(c, seq_dst, p1);
+    return true;
+    API_CATCH(false)
+}
+
 int32_t llmi_seq_pos_max(const struct llama_context* ctx, llama_seq_id seq_id) {
     if (!ctx || seq_id < 0 || seq_id >= ctx->c.n_seq) return -1;
     return seq_past_of(ctx->c, seq_id) - 1;

@@ -225,6 +225,12 @@ int32_t llmi_test_option(const char* name, int32_t value) {
         g_mv_unit_split = value;
         return old;
     }
+    if (!strcmp(name, "kv_cp_unroll")) {  // k_kv_seq_cp's items per thread: 0 auto (by the copy's size), 1, 4
+        const int old = g_kv_cp_unroll;
+        if (value >= 0 && value != 0 && value != 1 && value != 4) { set_err("llmi_test_option: kv_cp_unroll must be 0, 1 or 4"); return -2; }
+        if (value >= 0) g_kv_cp_unroll = value;
+        return old;
+    }
     if (!strcmp(name, "pf_attn_simple")) opt = &g_pf_attn_simple;
     else if (!strcmp(name, "mv_split_nt")) opt = &g_mv_split_nt;  // 0 auto (LLMI_MV_SPLIT_NT), 256, 512
     else if (!strcmp(name, "pf_fa_noalloc")) opt = &g_pf_fa_noalloc;
@@ -889,6 +895,38 @@ int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
     hipError_t e = launch_attention(a, n_head, n_head_kv, head_dim, kv_bucket_bound(n_kv, n_ctx), nullptr, mode);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_err(std::string("llmi_attention: ") + hip_err(e)); return -3; }
+    return 0;
+    API_CATCH(-5)
+}
+
+// k_kv_seq_cp alone over the caller's device memory (llama_kv_self_seq_cp's launch).  Every
+// refusal comes before the first device call, so a machine without a GPU can ask for them.
+int32_t llmi_kv_seq_copy(int32_t n_planes, int32_t head_dim, int32_t n_ctx, int32_t p0, int32_t p1, const uint16_t* kc_src,
+                         const uint16_t* vc_src, const int32_t* hist_src, uint16_t* kc_dst, uint16_t* vc_dst,
+                         int32_t* hist_dst, double* usec) {
+    API_TRY
+    const std::string who = "llmi_kv_seq_copy: ";
+    const struct { const char* field; const void* p; } ptrs[] = {{"kc_src", kc_src}, {"vc_src", vc_src}, {"hist_src", hist_src},
+                                                                {"kc_dst", kc_dst}, {"vc_dst", vc_dst}, {"hist_dst", hist_dst}};
+    for (const auto& f : ptrs)
+        if (!f.p) { set_err(who + f.field + " is a null pointer"); return -1; }
+    if (n_planes <= 0) { set_err(who + "n_planes must be positive"); return -1; }
+    if (head_dim <= 0 || head_dim % 8) { set_err(who + "head_dim must be a positive multiple of 8"); return -1; }
+    if (n_ctx <= 0 || n_ctx % 256) { set_err(who + "n_ctx must be a positive multiple of 256"); return -1; }
+    if (p0 < 0 || p0 >= p1) { set_err(who + "p0 outside 0 <= p0 < p1"); return -1; }
+    if (p1 > n_ctx) { set_err(who + "p1 beyond n_ctx"); return -1; }
+    KvCopyArgs a;
+    a.kc_src = kc_src; a.vc_src = vc_src; a.hist_src = hist_src;
+    a.kc_dst = kc_dst; a.vc_dst = vc_dst; a.hist_dst = hist_dst;
+    a.n_planes = n_planes; a.head_dim = head_dim; a.n_ctx = n_ctx; a.p0 = p0; a.p1 = p1;
+    if (!kv_seq_cp_ok(a)) { set_err(who + "n_planes * head_dim too large"); return -1; }
+    const int cap = hook_grid_cap();
+    if (cap <= 0) { set_err(who + "device query failed"); return -2; }
+    HipObjs h;
+    auto launch = [&] { return launch_kv_seq_cp(a, cap, nullptr); };
+    hipError_t e = usec ? time_launch(h, launch, *usec) : launch();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_err(who + hip_err(e)); return -3; }
     return 0;
     API_CATCH(-5)
 }

@@ -24,6 +24,7 @@ constexpr int kPfAttnMaxKV = 32768;  // batched-prefill attention: scores of one
 // test options (llmi_test_option in capi_hooks.cpp): bit-identical path selection and lowered limits
 extern int g_mv_unit_split, g_mv_split_nt;  // matvec unit split (kernels.hip LLMI_MV_SPLIT: -1 auto, 0 .. 3) and the workgroup threads of split launches (0 auto, 256, 512)
 extern int g_pf_fa_noalloc, g_pf_gemm_ng, g_pf_qkv_merge, g_pf_xcd_map, g_pf_quant_bpc, g_pf_quant_split_below, g_pf_attn_simple, g_pf_attn_fa, g_pf_fa_cfg, g_pf_max_kv, g_xspin_limit, g_xtag_skew;
+extern int g_kv_cp_unroll;  // k_kv_seq_cp's items per thread (kvcopy.hip: 0 auto, 1, 4)
 int pf_max_kv();  // llama_decode hands prompt runs reaching past this KV length to decode steps
 // scratch floats an attention context needs: scores [H][n_ctx] + tile maxima [H][n_ctx/32]
 // + k_attn_x's 8-byte {tag, score} granules [H][kXAttnMaxKV] + a fault word
@@ -448,5 +449,26 @@ struct LogprobArgs {
 };
 hipError_t launch_logprob(const LogprobArgs& a, int slots, hipStream_t stream);
 hipError_t launch_logprob_pick(const LogprobArgs& a, int slots, hipStream_t stream);
+
+// llama_kv_self_seq_cp on the device (kvcopy.hip, k_kv_seq_cp): positions [p0, p1) of one
+// sequence's K cache [n_planes][n_ctx][head_dim], transposed V cache [n_planes][head_dim][n_ctx]
+// (n_planes = n_layer * n_head_kv) and token history [n_ctx] into another's, bit for bit, in
+// one launch.  Nothing of dst outside [p0, p1) is written, nothing of src at all.
+struct KvCopySec {  // one of the launch's three 2-D copies as tiles (filled by launch_kv_seq_cp)
+    unsigned rows = 0, width = 0, shift = 0, ushift = 0, tiles_w = 0;
+    unsigned long long tiles = 0;
+};
+struct KvCopyArgs {
+    const uint16_t *kc_src = nullptr, *vc_src = nullptr;
+    const int32_t* hist_src = nullptr;
+    uint16_t *kc_dst = nullptr, *vc_dst = nullptr;
+    int32_t* hist_dst = nullptr;
+    int n_planes = 0, head_dim = 0, n_ctx = 0, p0 = 0, p1 = 0;
+    KvCopySec sec[3];  // K, V, hist
+};
+// head_dim a positive multiple of 8, n_ctx of 256, 0 <= p0 < p1 <= n_ctx, no null pointer
+bool kv_seq_cp_ok(const KvCopyArgs& a);
+// max_blocks: the context's matvec grid cap (mv_grid_cap); the grid is sized from it
+hipError_t launch_kv_seq_cp(const KvCopyArgs& a, int max_blocks, hipStream_t stream);
 
 }  // namespace llmi

@@ -366,6 +366,21 @@ def logprob_rows(logits, history, params: Sequence, uniforms, n_top: Sequence[in
             "rows": after, "usec": tuple(us)}
 
 
+def kv_seq_copy(n_planes: int, head_dim: int, n_ctx: int, p0: int, p1: int, kc_src: int, vc_src: int, hist_src: int,
+                kc_dst: int, vc_dst: int, hist_dst: int) -> float:
+    """llmi_kv_seq_copy: k_kv_seq_cp alone (Context.seq_cp's launch) over device addresses:
+    positions [p0, p1) of the src K cache [n_planes][n_ctx][head_dim] f16, transposed V cache
+    [n_planes][head_dim][n_ctx] f16 and history [n_ctx] int32 into the dst ones.  Returns the
+    launch's event-timed device microseconds; bad arguments raise before any device call."""
+    us = C.c_double()
+    vp = lambda a: C.c_void_p(int(a)) if a else None  # noqa: E731
+    r = lib().llmi_kv_seq_copy(int(n_planes), int(head_dim), int(n_ctx), int(p0), int(p1), vp(kc_src), vp(vc_src),
+                               vp(hist_src), vp(kc_dst), vp(vc_dst), vp(hist_dst), C.byref(us))
+    if r != 0:
+        raise LlmiError(f"llmi_kv_seq_copy returned {r}: {last_error()}")
+    return us.value
+
+
 # the device's StepState (llmi_step_state) as a NumPy record
 STEP_STATE = np.dtype([("token_in", "<i4"), ("token_in_pos", "<i4"), ("pos_next", "<i4"), ("pos", "<i4"), ("token", "<i4"),
                        ("seq", "<u4"), ("key", "<u8", (2, 64))])
@@ -557,6 +572,12 @@ class Context:
     def seq_rm(self, seq: int, p0: int = 0, p1: int = -1) -> bool:
         """llama_kv_self_seq_rm (tail removal)."""
         return bool(lib().llama_kv_self_seq_rm(self._h, int(seq), int(p0), int(p1)))
+
+    def seq_cp(self, src: int, dst: int, p0: int = 0, p1: int = -1) -> bool:
+        """llama_kv_self_seq_cp: positions [p0, p1) of sequence src into sequence dst on the
+        device (p1 < 0: all src holds); dst's past becomes p1.  False (last_error() says why) for
+        a bad sequence, src == dst, a range src does not hold or one that would leave a hole."""
+        return bool(lib().llama_kv_self_seq_cp(self._h, int(src), int(dst), int(p0), int(p1)))
 
     def seq_pos_max(self, seq: int) -> int:
         return int(lib().llmi_seq_pos_max(self._h, int(seq)))

@@ -197,6 +197,7 @@ SIGNATURES = {
     "llmi_sample_logits": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(llmi_sampler_params), _P, _P, _P,
                                        _P, _P, C.POINTER(C.c_double)]),
     "llama_kv_self_seq_rm": (C.c_bool, [_P, C.c_int32, C.c_int32, C.c_int32]),
+    "llama_kv_self_seq_cp": (C.c_bool, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "llmi_seq_pos_max": (C.c_int32, [_P, C.c_int32]),
     "llmi_model_upload_s": (C.c_double, [_P]),
     "llmi_last_step_stats": (None, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -215,6 +216,8 @@ SIGNATURES = {
     "llmi_model_arena_hash": (C.c_int32, [_P, C.POINTER(C.c_uint64)]),
     "llmi_device_hash": (C.c_int32, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "llmi_attention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32]),
+    "llmi_kv_seq_copy": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                     C.POINTER(C.c_double)]),
     "llmi_attn_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "llmi_attn_x86_form": (C.c_int32, [C.c_int32, C.c_int32]),
     "llmi_battention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _P, _P,

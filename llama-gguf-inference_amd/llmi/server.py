@@ -56,6 +56,21 @@ one scheduler thread: requests go to the least-loaded replica and are decoded th
 together, one batched step per token for up to 8 sequences (continuous batching,
 SURVEY.md §8f row 3).
 
+Prompt cache (llama-server's cache_prompt; opt-in here: `--cache-prompt` or
+LLMI_CACHE_PROMPT=1, because it adds a field to `usage`): a replica remembers, for each of
+its sequences, the tokens whose KV rows the sequence holds, and a new request prefills only
+what differs.  It goes to the free sequence that shares the longest prefix with its prompt
+(ties: the least recently used); if another sequence of the replica, free or busy, shares a
+longer one, the difference is copied on the device (llama_kv_self_seq_cp, one launch) instead
+of prefilled; at least the prompt's last token is always decoded.  A request served from the
+cache gets the logits and tokens of the same request served cold, bit for bit.  `cache_prompt:
+false` in a request, `--no-cache-prompt` or LLMI_CACHE_PROMPT=0 (the variable is read when a
+replica starts and, when set, wins over the flags; A/B) prefill the whole prompt as before.
+While the cache is on, responses carry
+usage.prompt_tokens_details.cached_tokens (native /completion: tokens_cached) and each
+replica's /health entry the totals prompt_tokens and cached_tokens; among equally loaded
+replicas a request goes to the one that holds the longest prefix of its prompt.
+
 Text: the GGUF's own tokenizer (SPM or byte-level BPE from tokenizer.ggml.*) and chat
 template (tokenizer.chat_template, sandboxed Jinja2), llmi/tokenizer.py; streamed text
 holds incomplete UTF-8 sequences back until their last byte.
@@ -223,12 +238,16 @@ class Request:
     fed by its generator's uniforms, or on the host over each step's logits (Replica._step).
     `stop`: strings that end the generation (checked on the detokenized output).
     `n_top` >= 0: every token comes with its log-probability entry (host_logprob_entry's
-    shape) in `lp`, parallel to `out`."""
+    shape) in `lp`, parallel to `out`.  `cached`: how many of the prompt's positions the
+    replica's prompt cache supplied (set at admission)."""
 
     def __init__(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
-                 sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None, n_top: int = -1):
+                 sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None, n_top: int = -1,
+                 cache_prompt: bool = True):
         self.prompt, self.max_tokens, self.ignore_eos = list(prompt), max_tokens, ignore_eos
         self.n_top = n_top
+        self.cache_prompt = cache_prompt  # False: the whole prompt is prefilled (llama-server's field)
+        self.cached = 0                   # prompt positions served from the replica's prompt cache
         self.lp: list[tuple] = []
         self.sampler = Sampler(sampling) if sampling is not None and not sampling.greedy else None
         self.stop = list(stop or [])
@@ -262,14 +281,25 @@ class Request:
         self.q.put(None)
 
 
+def _common_prefix(a: list[int], b: list[int]) -> int:
+    n = min(len(a), len(b))
+    if a[:n] == b[:n]:
+        return n
+    i = 0
+    while a[i] == b[i]:
+        i += 1
+    return i
+
+
 class Replica:
     """One context (device) serving up to `slots` requests at once.  Its thread admits
     queued requests into free sequences (prefill through llama_decode with their seq id)
     and advances all active ones together with llmi_generate_greedy_batch (one weight
-    stream per step for up to 8 sequences), `chunk` tokens per call."""
+    stream per step for up to 8 sequences), `chunk` tokens per call.  With the prompt cache
+    (cache_prompt) it keeps what each sequence holds and prefills only what a prompt adds."""
 
     def __init__(self, idx: int, ctx, slots: int, eog: set, chunk: int, n_ctx: int, device: int = 0,
-                 detok: Optional[Callable[[list[int]], str]] = None):
+                 detok: Optional[Callable[[list[int]], str]] = None, cache_prompt: bool = False):
         self.idx, self.ctx, self.slots, self.eog, self.chunk, self.n_ctx = idx, ctx, slots, eog, chunk, n_ctx
         self.device = device
         self.detok = detok
@@ -287,6 +317,17 @@ class Replica:
         self.device_sampling = hasattr(ctx, "generate_sampled_batch") and os.environ.get("LLMI_DEVICE_SAMPLING", "1") != "0"
         # device log-probabilities: the same, and the context has that call too
         self.device_logprobs = self.device_sampling and hasattr(ctx, "generate_logprobs_batch")
+        # prompt cache: asked for (--cache-prompt; LLMI_CACHE_PROMPT, when set, decides instead:
+        # 0 off, else on), and the context can copy between sequences
+        env = os.environ.get("LLMI_CACHE_PROMPT")
+        self.cache_prompt = (cache_prompt if env is None else env != "0") and hasattr(ctx, "seq_cp")
+        # per sequence: the tokens whose KV rows it holds (never more than what was fed), and
+        # when it was last admitted into or released (the scheduler's admission count)
+        self.held: list[list[int]] = [[] for _ in range(slots)]
+        self.used = [0] * slots
+        self.tick = 0
+        self.prompt_tokens = 0   # prompt tokens admitted / of them served from the cache
+        self.cached_tokens = 0
         self.th = threading.Thread(target=self._run, name=f"llmi-replica-{idx}", daemon=True)
         self.th.start()
 
@@ -309,24 +350,88 @@ class Replica:
         except Exception:
             pass
 
+    # -- the prompt cache's bookkeeping
+    def prefix_len(self, prompt: list[int]) -> int:
+        """The longest prefix of prompt that one of this replica's sequences holds."""
+        with self.lock:
+            return max(_common_prefix(prompt, h) for h in self.held)
+
+    def _touch(self, seq: int) -> None:
+        self.tick += 1
+        self.used[seq] = self.tick
+
+    def _remember(self, r: Request) -> None:
+        """r's sequence holds (r.prompt + r.out)[:r.pos]: tokens a chunk fed past the
+        request's end are not part of it."""
+        if not self.cache_prompt:
+            return
+        n = min(r.pos, len(r.prompt) + len(r.out)) - len(r.prompt)
+        with self.lock:
+            h = self.held[r.seq]
+            h += r.out[len(h) - len(r.prompt):n]
+
+    def _forget(self, seq: int) -> None:
+        with self.lock:
+            self.held[seq] = []
+
+    def _release(self, r: Request) -> None:
+        self._touch(r.seq)
+        self.free.append(r.seq)
+
+    def _place(self, r: Request) -> tuple[int, int, int, int]:
+        """Takes the free sequence r goes to off the free list: the one sharing the longest
+        prefix with its prompt (ties: least recently used, then the last of the free list).
+        Returns it, the length of that prefix, and the sequence of this replica (free or
+        decoding) that shares the longest prefix of all, with its length.  (cache_prompt
+        false: the sequence the request always went to, nothing shared.)"""
+        if not r.cache_prompt:
+            return self.free.pop(), 0, -1, 0
+        lens = [_common_prefix(r.prompt, h) for h in self.held]
+        seq = max(self.free, key=lambda s: (lens[s], -self.used[s], self.free.index(s)))
+        self.free.remove(seq)
+        t = max(range(self.slots), key=lambda s: (lens[s], -s))
+        return seq, lens[seq], t, lens[t]
+
     # -- admission: prefill into a free sequence, emit the first token
     def _admit(self, r: Request) -> None:
         with self.lock:
             self.n_queued -= 1
-        seq = self.free.pop()
+        cache = self.cache_prompt
+        seq = -1
         try:
             c = self.ctx
-            c.seq_rm(seq)
+            if not cache:
+                seq, have = self.free.pop(), 0
+                c.seq_rm(seq)
             max_tokens = r.max_tokens
             if len(r.prompt) + max_tokens > self.n_ctx:
                 max_tokens = max(0, self.n_ctx - len(r.prompt))
             r.max_tokens = max_tokens
             if not r.prompt or max_tokens <= 0:
-                self.free.append(seq)
+                if seq >= 0:
+                    self.free.append(seq)
                 r.done("length")
                 return
+            if cache:
+                seq, have, t, upto = self._place(r)
+                # another sequence holds more of the prompt: the difference is copied on the
+                # device.  t may be decoding: its prefix rows are stable, and this thread alone
+                # uses the context.  (A refused copy leaves seq as it was: prefilled instead.)
+                if upto > have and len(r.prompt) > 1 and c.seq_cp(t, seq, have, upto):
+                    have = upto
+                    with self.lock:
+                        self.held[seq] = list(r.prompt[:have])
+            # at least the last token is decoded: the first token is sampled from its logits
+            n = min(have, len(r.prompt) - 1)
+            if cache:
+                self._touch(seq)
+                self._forget(seq)  # until the decode below has succeeded
+                c.seq_rm(seq, n, -1) if n > 0 else c.seq_rm(seq)
             t0 = time.perf_counter()
-            rc = c.decode(r.prompt, seq=[seq] * len(r.prompt))
+            if n > 0:
+                rc = c.decode(r.prompt[n:], pos=list(range(n, len(r.prompt))), seq=[seq] * (len(r.prompt) - n))
+            else:
+                rc = c.decode(r.prompt, seq=[seq] * len(r.prompt))
             self.busy_s += time.perf_counter() - t0
             if rc != 0:
                 raise RuntimeError(f"llama_decode returned {rc}")
@@ -334,13 +439,21 @@ class Replica:
             # the first token's entry: from the prompt's logits on the host, on every path
             entries = [host_logprob_entry(c.logits(-1), first, r.n_top)] if r.n_top >= 0 else None
             r.seq, r.pos = seq, len(r.prompt)
+            if cache:
+                r.cached = n
+                with self.lock:
+                    self.held[seq] = list(r.prompt)
+                    self.prompt_tokens += len(r.prompt)
+                    self.cached_tokens += n
             if self._take(r, [first], entries):
-                self.free.append(seq)
+                self._release(r)
             else:
                 r.last = first
                 self.active.append(r)
         except Exception as e:  # this request fails; the replica keeps serving
-            self.free.append(seq)
+            if seq >= 0:
+                self._forget(seq)
+                self.free.append(seq)
             r.fail(str(e))
 
     def _take(self, r: Request, toks: list[int], entries: Optional[list[tuple]] = None) -> bool:
@@ -455,11 +568,13 @@ class Replica:
             toks = outs[id(r)]
             r.pos += len(toks)
             r.last = toks[-1]
-            if self._take(r, toks, lps.get(id(r))):
+            fin = self._take(r, toks, lps.get(id(r)))
+            self._remember(r)
+            if fin:
                 done.append(r)
         for r in done:
             self.active.remove(r)
-            self.free.append(r.seq)
+            self._release(r)
         # rotate so more than 8 active requests share the steps fairly
         if len(self.active) > 8:
             self.active = self.active[len(batch):] + self.active[:len(batch)]
@@ -479,6 +594,7 @@ class Replica:
                 self._step()
             except Exception as e:  # the context failed: every active request fails
                 for r in self.active:
+                    self._forget(r.seq)  # its rows are not to be trusted
                     r.fail(str(e))
                     self.free.append(r.seq)
                 self.active = []
@@ -486,12 +602,16 @@ class Replica:
 
 class Engine:
     """Owns the GPU replicas.  Requests go to the least-loaded replica (active + queued;
-    ties to the lowest index) and are served there with continuous batching."""
+    ties to the one whose prompt cache holds the longest prefix of the prompt, then to the
+    lowest index) and are served there with continuous batching."""
 
     def __init__(self, path: str, n_ctx: int, n_gpu_layers: int, devices: list[int], slots: int = 4,
                  chunk: int = 8, contexts=None, sampling: Optional[SamplingParams] = None, numerics: int = 0,
-                 max_logprobs: int = 0):
+                 max_logprobs: int = 0, cache_prompt: bool = False):
         self.path, self.n_ctx, self.ngl, self.devices = path, n_ctx, n_gpu_layers, devices
+        # the replicas' prompt cache (--cache-prompt); whether it is active is decided per
+        # replica when it starts (Replica.cache_prompt), see prompt_cache
+        self.cache_prompt = cache_prompt
         # alternatives a request may ask for (--max-logprobs); 0: logprobs are refused with a 400
         self.max_logprobs = max(0, min(int(max_logprobs), MAX_LOGPROBS))
         self.numerics = numerics  # llmi.NUMERICS_GENERIC / NUMERICS_X86 (DESIGN.md §5)
@@ -534,7 +654,7 @@ class Engine:
             eog = getattr(self.vocab, "eog", {self.vocab.eos})
             detok = getattr(self.vocab, "detokenize", None)
             self.replicas = [Replica(i, c, self.slots, eog, self.chunk, self.n_ctx,
-                                     self.devices[i] if i < len(self.devices) else i, detok)
+                                     self.devices[i] if i < len(self.devices) else i, detok, self.cache_prompt)
                              for i, c in enumerate(ctxs)]
             self.load_s = time.perf_counter() - t0
             self.t_ready = time.perf_counter()
@@ -543,10 +663,38 @@ class Engine:
             self.error = str(e)
 
     def submit(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
-               sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None, n_top: int = -1) -> Request:
-        r = Request(prompt, max_tokens, ignore_eos, sampling, stop, n_top)
-        rep = min(self.replicas, key=lambda x: (x.load(), x.idx))
+               sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None, n_top: int = -1,
+               cache_prompt: bool = True) -> Request:
+        r = Request(prompt, max_tokens, ignore_eos, sampling, stop, n_top, cache_prompt)
+        loads = [x.load() for x in self.replicas]
+        tied = [x for x, n in zip(self.replicas, loads) if n == min(loads)]
+        if len(tied) > 1 and cache_prompt and self.prompt_cache:
+            rep = min(tied, key=lambda x: (-(x.prefix_len(r.prompt) if x.cache_prompt else 0), x.idx))
+        else:
+            rep = tied[0]
         rep.submit(r)
+        return r
+
+    @property
+    def prompt_cache(self) -> bool:
+        """Is the prompt cache active on a replica?  (Then responses report cached tokens.)"""
+        return any(x.cache_prompt for x in self.replicas)
+
+    def run(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
+            on_tokens: Callable[[list[int], Optional[list[tuple]]], None], sampling: Optional[SamplingParams] = None,
+            stop: Optional[list[str]] = None, n_top: int = -1, cache_prompt: bool = True) -> Request:
+        """Serve one request to its end, handing its tokens (and, with n_top >= 0, their logprob
+        entries) to on_tokens as they come; returns the finished Request (out, finish, lp, cached)."""
+        r = self.submit(prompt, max_tokens, ignore_eos, sampling, stop, n_top, cache_prompt)
+        seen = 0
+        while True:
+            toks = r.q.get()
+            if toks is None:
+                break
+            on_tokens(toks, r.lp[seen:seen + len(toks)] if n_top >= 0 else None)
+            seen += len(toks)
+        if r.error:
+            raise RuntimeError(r.error)
         return r
 
     def generate(self, prompt: list[int], max_tokens: int, ignore_eos: bool, on_tokens: Callable[[list[int]], None],
@@ -562,16 +710,7 @@ class Engine:
                           n_top: int = -1) -> tuple[list[int], str, list[tuple]]:
         """generate with each token's logprob entry (n_top >= 0; else None) handed to
         on_tokens along with the tokens; returns (tokens, finish, entries)."""
-        r = self.submit(prompt, max_tokens, ignore_eos, sampling, stop, n_top)
-        seen = 0
-        while True:
-            toks = r.q.get()
-            if toks is None:
-                break
-            on_tokens(toks, r.lp[seen:seen + len(toks)] if n_top >= 0 else None)
-            seen += len(toks)
-        if r.error:
-            raise RuntimeError(r.error)
+        r = self.run(prompt, max_tokens, ignore_eos, on_tokens, sampling, stop, n_top)
         return r.out, r.finish or "length", r.lp
 
     def health(self) -> dict:
@@ -583,6 +722,8 @@ class Engine:
             reps.append({"id": r.idx, "device": r.device, "active": len(r.active), "queued": r.n_queued,
                          "tokens": r.tokens, "tok_s": round(r.tokens / max(r.busy_s, 1e-9), 1) if r.tokens else 0.0,
                          "hbm_gbps": round(r.last_gbps, 1), "busy": round(r.busy_s / up, 3)})
+            if r.cache_prompt:
+                reps[-1].update(prompt_tokens=r.prompt_tokens, cached_tokens=r.cached_tokens)
         busy = sum(len(r.active) for r in self.replicas)
         return {"slots_idle": self.slots * len(self.replicas) - busy, "slots_processing": busy,
                 "load_s": round(self.load_s, 2), "replicas": reps[:16]}
@@ -755,17 +896,33 @@ class Handler(BaseHTTPRequestHandler):
             n_top = self._logprobs_wanted(req, route, getattr(eng, "max_logprobs", 0))
             sampling = getattr(eng, "sampling", SamplingParams()).with_request(req)
             stop = parse_stop(req.get("stop"))
+            cache_prompt = req.get("cache_prompt", True)
+            if not isinstance(cache_prompt, bool):
+                raise ValueError("'cache_prompt' must be a boolean")
         except (ValueError, TypeError) as e:
             return self._send_json(400, _error(400, str(e), "invalid_request_error"))
+        # the prompt cache is on: the engine's run() also tells how much of the prompt it served
+        cache_on = bool(getattr(eng, "prompt_cache", False))
+
+        def usage(n_out: int, cached: Optional[int]) -> dict:
+            u = {"prompt_tokens": len(prompt), "completion_tokens": n_out, "total_tokens": len(prompt) + n_out}
+            if cached is not None:
+                u["prompt_tokens_details"] = {"cached_tokens": cached}
+            return u
         ignore_eos = bool(req.get("ignore_eos", False))
         stream = bool(req.get("stream", False))
         rid = ("chatcmpl-" if chat else "cmpl-") + uuid.uuid4().hex[:24]
         created = int(time.time())
         obj = "chat.completion" if chat else "text_completion"
         if not stream:
-            entries = None
+            entries, cached = None, None
             try:
-                if n_top >= 0:
+                if cache_on:
+                    r = eng.run(prompt, max_tokens, ignore_eos, lambda _t, _e: None, sampling=sampling, stop=stop,
+                                n_top=n_top, cache_prompt=cache_prompt)
+                    ids, finish, cached = r.out, r.finish or "length", r.cached
+                    entries = r.lp if n_top >= 0 else None
+                elif n_top >= 0:
                     ids, finish, entries = eng.generate_logprobs(prompt, max_tokens, ignore_eos, lambda _t, _e: None,
                                                                  chunk=32, sampling=sampling, stop=stop, n_top=n_top)
                 else:
@@ -791,10 +948,11 @@ class Handler(BaseHTTPRequestHandler):
                 lj = self._logprob_json(route, ids[:keep], entries[:keep], starts[:keep])
                 choice["logprobs"] = lj.pop("logprobs")
                 extra = lj
+            if cached is not None and route == "/completion":
+                extra["tokens_cached"] = cached
             return self._send_json(200, {
                 "id": rid, "object": obj, "created": created, "model": eng.model_id, "choices": [choice],
-                "usage": {"prompt_tokens": len(prompt), "completion_tokens": len(ids),
-                          "total_tokens": len(prompt) + len(ids)},
+                "usage": usage(len(ids), cached),
                 "llmi": {"tokens": ids}, **extra})
         # SSE: headers, one data: line per token batch, final chunk, [DONE], close
         self.send_response(200)
@@ -842,7 +1000,12 @@ class Handler(BaseHTTPRequestHandler):
                 chunk_of(piece)
 
         try:
-            if n_top >= 0:
+            cached = None
+            if cache_on:
+                r = eng.run(prompt, max_tokens, ignore_eos, on_tokens, sampling=sampling, stop=stop, n_top=n_top,
+                            cache_prompt=cache_prompt)
+                ids, finish, cached = r.out, r.finish or "length", r.cached
+            elif n_top >= 0:
                 ids, finish, _ = eng.generate_logprobs(prompt, max_tokens, ignore_eos, on_tokens, chunk=4,
                                                        sampling=sampling, stop=stop, n_top=n_top)
             else:
@@ -855,8 +1018,8 @@ class Handler(BaseHTTPRequestHandler):
             last = ({"index": 0, "delta": {}, "finish_reason": finish} if chat
                     else {"index": 0, "text": "", "logprobs": None, "finish_reason": finish})
             event({"id": rid, "object": cobj, "created": created, "model": eng.model_id, "choices": [last],
-                   "usage": {"prompt_tokens": len(prompt), "completion_tokens": len(ids),
-                             "total_tokens": len(prompt) + len(ids)}})
+                   "usage": usage(len(ids), cached), **({"tokens_cached": cached} if cached is not None and
+                                                        route == "/completion" else {})})
             self.wfile.write(b"data: [DONE]\n\n")
             self.wfile.flush()
         except (BrokenPipeError, ConnectionResetError):
@@ -894,6 +1057,12 @@ def parse_args(argv=None):
     ap.add_argument("--max-logprobs", type=int, default=int(os.environ.get("LLMI_MAX_LOGPROBS", "0")),
                     help=f"most top_logprobs / logprobs / n_probs a request may ask for, at most {MAX_LOGPROBS} "
                          "(0, the default: requests for logprobs get a 400)")
+    ap.add_argument("--cache-prompt", dest="cache_prompt", action="store_true", default=False,
+                    help="prompt cache: prefill only what a prompt adds to what a slot already holds, copy a "
+                         "prefix another slot holds (also LLMI_CACHE_PROMPT=1); responses then report cached_tokens")
+    ap.add_argument("--no-cache-prompt", dest="cache_prompt", action="store_false",
+                    help="prefill every prompt in full (the default; also LLMI_CACHE_PROMPT=0, or "
+                         "cache_prompt: false in a request)")
     ap.add_argument("--numerics", choices=NUMERICS_CHOICES, default=None,
                     help="fp32 association of every kernel: ggml's generic order, or the oracle's model of "
                          "upstream's x86 AVX2 association (non-repack); '-fa': decode attention in ggml's CPU "
@@ -945,7 +1114,7 @@ def main(argv=None) -> int:
                         presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty, seed=args.seed)
     eng = Engine(args.model, args.ctx_size, args.ngl, list(range(max(1, args.replicas))), slots=args.parallel,
                  chunk=args.decode_chunk, sampling=sp, numerics=numerics_value(args.numerics),
-                 max_logprobs=args.max_logprobs)
+                 max_logprobs=args.max_logprobs, cache_prompt=args.cache_prompt)
     srv = make_server(eng, args.host, args.port, key)
     threading.Thread(target=eng.load, daemon=True).start()
     print(f"[llmi-server] listening on {args.host}:{args.port}", file=sys.stderr, flush=True)
