@@ -715,9 +715,15 @@ template <int D>
 __global__ __launch_bounds__(D) void k_attl_sum(AttnArgs a, int n_head) { attl_sum_body<D>(a, n_head); }
 
 // Dim-split one-launch attention (path 6): body in attn_device.h (shared with k_battn_d)
+// What the entry needs arrives as plain scalars and pointers, which are preloaded into
+// SGPRs (14 dwords: 5 pointers, n_ctx, geo = G | HK << 8 | pf << 24, kvb, scale)
 template <int D, int P, int S>
-__global__ __launch_bounds__(512) void k_attn_d(AttnArgs a, int G, int HK, int kvb, int pf) {
-    attn_d_body<D, P, S>(a, G, HK, kvb, pf & 1, (pf >> 1) & 1);
+__global__ __launch_bounds__(512) void k_attn_d(const float* q, const uint16_t* kc, const uint16_t* vc, const StepState* st,
+                                                float* out, int n_ctx, int geo, int kvb, float scale,
+                                                unsigned long long* trace) {
+    const int pf = geo >> 24;
+    attn_d_body<D, P, S>(AttnDArgs{q, kc, vc, st, out, n_ctx, scale, trace}, geo & 255, (geo >> 8) & 0xffff, kvb, pf & 1,
+                         (pf >> 1) & 1);
 }
 
 // ---- Selection: which path, and each path's P / S / NP / tile counts, for the single-
@@ -884,7 +890,8 @@ hipError_t launch_attention(const AttnArgs& a0, int n_head, int n_head_kv, int h
             break;
         case 6:
             ok = pick([&](auto D, auto P, auto S) {
-                launch_k(k_attn_d<D, P, S>, dim3(n_head * S), dim3(512), 0, s, true, true, a, g, hk, kv_bound, g_attn_pf);
+                launch_k(k_attn_d<D, P, S>, dim3(n_head * S), dim3(512), 0, s, true, true, a.q, a.kc, a.vc, a.st, a.out,
+                         a.n_ctx, g | hk << 8 | g_attn_pf << 24, kv_bound, a.scale, a.trace);
             }, d, Of<1, 2, 4, 8, 12, 16>{attn_passes(kv_bound, 16)}, Of<2, 4, 8>{attn_d_slices(n_head, head_dim)});
             break;
         case 7:

@@ -439,6 +439,37 @@ __device__ __forceinline__ void attl_sum_body(const AttnArgs& a, int n_head) {
     a.out[(size_t)h * D + d] = (float)s;
 }
 
+// What attn_d_body reads of an attention launch.  k_attn_d takes these as leading scalar
+// kernel arguments, which gfx950 preloads into SGPRs at wave launch (Makefile
+// -amdgpu-kernarg-preload-count): no kernarg round trip ahead of the first load.
+struct AttnDArgs {
+    const float* q;
+    const uint16_t* kc;
+    const uint16_t* vc;
+    const StepState* st;
+    float* out;
+    int n_ctx;
+    float scale;
+    unsigned long long* trace;  // LLMI_EXP_TRACE builds
+};
+__device__ __forceinline__ AttnDArgs attn_d_args(const AttnArgs& a) {
+    return {a.q, a.kc, a.vc, a.st, a.out, a.n_ctx, a.scale, a.trace};
+}
+
+// The step position, requested by the wave's first instruction and waited for where it is
+// first needed.  In plain C++ the compiler sinks the scalar load below the loads that do not
+// depend on it; the pair below pins where it is issued.  The compiler's own wait counting
+// does not see this load: step_pos_wait() must stand between the request and the first use.
+__device__ __forceinline__ int step_pos_request(const StepState* st) {
+    int pos;
+    asm volatile("s_load_dword %0, %1, %2" : "=s"(pos) : "s"(st), "n"(offsetof(StepState, pos)));
+    return pos;
+}
+__device__ __forceinline__ int step_pos_wait(int pos) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(pos));
+    return pos;
+}
+
 // Dim-split one-launch attention (path 6, kv_bound <= 64*P <= 1024): H*S workgroups of
 // 512 threads.  Workgroup b serves query head h of KV group g = b % HK and the DS = D/S
 // output dims of slice b / H.  Each workgroup recomputes its head's scores and softmax
@@ -451,7 +482,7 @@ __device__ __forceinline__ void attl_sum_body(const AttnArgs& a, int n_head) {
 // sum)), double PV); the per-position work and the PV lane split differ only in how the
 // exact double sums are associated.
 template <int D, int P, int S>
-__device__ __forceinline__ void attn_d_body(const AttnArgs& a, int G, int HK, int kvb, int pf = 0, int rot_on = 0) {
+__device__ __forceinline__ void attn_d_body(const AttnDArgs& a, int G, int HK, int kvb, int pf = 0, int rot_on = 0) {
     constexpr int DQ = D / 8;                    // score dims per lane
     constexpr int DS = D / S;                    // output dims of this workgroup
     constexpr int SLV = 512 / DS;                // PV lanes per output dim (<= 64)
@@ -460,16 +491,22 @@ __device__ __forceinline__ void attn_d_body(const AttnArgs& a, int G, int HK, in
     __shared__ __attribute__((aligned(16))) float sp[64 * P + 8];
     __shared__ float redm[8];
     __shared__ double reds[8];
+    const int pos_req = step_pos_request(a.st);
     LLMI_ATT_STAMP(0, 0)
     const int b = blockIdx.x, H = HK * G;
     const int g = b % HK, h = g * G + (b / HK) % G, ds = b / H;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qd = tid & 7, pp = tid >> 3;
-    // 1. every load up front: position, q slice, the K rows of all passes, the V slice.
-    // pf (the default): the K passes / V loads past the position are skipped (uniform
-    // branches on the position read first) instead of loading the whole KV bucket
-    const int pos = a.st->pos;
-    const int lim = pf ? pos + 1 : kvb;
+    // 1. every load up front, in two groups.  The position is requested first; q and the K
+    // passes that lie wholly below kvb - 256 are issued without waiting for it: a step in
+    // this 256-position bucket (kv_bucket_bound, capped at n_ctx) has pos >= kvb - 256, so
+    // those passes are live in every step of the bucket.  (Nothing rests on that rule: the
+    // rows are inside the cache for any kvb <= n_ctx, and a pass at or past the position is
+    // skipped by the scores below whether or not it was loaded.)  The passes that overlap
+    // the bucket's last 256 positions and the V slice follow once the position has arrived.
+    // pf (the default): of those, the K passes / V loads past the position are skipped
+    // (uniform branches) instead of loading the whole KV bucket
+    const int live = kvb - 256;
     // rot_on (the default): the workgroups of one KV group (one XCD) start their K passes
     // at different positions, so the requests for a K row are spread over the issue window
     // and the later ones hit that XCD's L2 (3-8 % faster, profiles/r02/attn_dim_split.md);
@@ -480,16 +517,40 @@ __device__ __forceinline__ void attn_d_body(const AttnArgs& a, int G, int HK, in
 #pragma unroll
     for (int i = 0; i < DQ / 4; ++i) qv[i] = *(const float4*)(a.q + (size_t)h * D + qd * DQ + 4 * i);
     u32x4 kv[P][DQ / 8];
+    auto k_row = [&](int p) {
+        const int t = min(64 * pb(p) + pp, kvb - 1);
+        return a.kc + ((size_t)g * a.n_ctx + t) * D + qd * DQ;
+    };
+    // (Passes and V loads that are skipped are never read: the scores and the PV below skip
+    // them under the same tests.  Where the registers of a skipped pass are zeroed and where
+    // they are left unset decides what the compiler does in the middle of the loads: zeroed
+    // in the single group of P <= 4, it copies a loaded register behind a vmcnt wait; left
+    // unset between the two groups of P > 4, it reuses the registers of a pass still in
+    // flight for address arithmetic, behind a wait again.  So P > 4 zeroes them in its
+    // early group and P <= 4 leaves them unset.  tools/entry_chain.py counts those waits;
+    // profiles/entry/ has the listings.)
+    constexpr bool EARLY = P > 4;  // kvb > 256: only then is there a pass below kvb - 256
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            if (64 * pb(p) + 64 <= live) {
+                const uint16_t* kr = k_row(p);
+#pragma unroll
+                for (int i = 0; i < DQ / 8; ++i) kv[p][i] = *(const u32x4*)(kr + 8 * i);
+            } else {
+#pragma unroll
+                for (int i = 0; i < DQ / 8; ++i) kv[p][i] = u32x4{0u, 0u, 0u, 0u};
+            }
+        }
+    }
+    const int pos = step_pos_wait(pos_req);
+    const int lim = pf ? pos + 1 : kvb;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-        const int t = min(64 * pb(p) + pp, kvb - 1);
-        const uint16_t* kr = a.kc + ((size_t)g * a.n_ctx + t) * D + qd * DQ;
-        if (64 * pb(p) < lim) {
+        if ((!EARLY || 64 * pb(p) + 64 > live) && 64 * pb(p) < lim) {
+            const uint16_t* kr = k_row(p);
 #pragma unroll
             for (int i = 0; i < DQ / 8; ++i) kv[p][i] = *(const u32x4*)(kr + 8 * i);
-        } else {
-#pragma unroll
-            for (int i = 0; i < DQ / 8; ++i) kv[p][i] = u32x4{0u, 0u, 0u, 0u};
         }
     }
     const int d = ds * DS + tid / SLV, sl = tid % SLV;
@@ -500,6 +561,9 @@ __device__ __forceinline__ void attn_d_body(const AttnArgs& a, int G, int HK, in
         if (8 * SLV * u < lim) vv[u] = *(const u32x4*)(vr + min(8 * sl + 8 * SLV * u, kvb - 8));
         else vv[u] = u32x4{0u, 0u, 0u, 0u};
     }
+    // the loads above are issued back to back: nothing that waits on one of them (the f16
+    // rounding of q, the first pass's products) may be scheduled among them
+    __builtin_amdgcn_sched_barrier(0);
     const int n_kv = pos + 1;
     // 2. scores (q rounded to f16 as upstream's KQ mul_mat does; f16 x f16 products exact)
     double q[DQ];

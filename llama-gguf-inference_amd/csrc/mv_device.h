@@ -300,6 +300,21 @@ __device__ __forceinline__ void quant_sub(const Lds& L, int cols, int sb, const 
     }
 }
 
+// Leading kernel arguments of k_matvec / k_matvec_split (mv_kernels.h): what stands on a
+// launch's entry chain -- the activation's addresses and size, the task ranges, the step state
+// -- as plain scalars and pointers, 14 dwords, which gfx950 preloads into SGPRs at wave launch
+// (Makefile -amdgpu-kernarg-preload-count), so that the activation loads wait for no kernarg
+// fetch.  Copies of MVArgs' fields of the same names: the entry reads these, everything
+// after it reads the struct, whose fetches are in flight beside the activation's.
+struct MVLead {
+    const float* x;
+    const float* nw;
+    const uint8_t* xq;
+    StepState* st;
+    int cols, ntasks, split_wgs, split_tasks, lr, rpt;
+    int nwg;  // gridDim.x
+};
+
 // Prologue in two halves so a caller can put the weight prefetch between them:
 // issue() loads this thread's first NP sub-blocks of x (and norm w) into registers —
 // UNCONDITIONALLY (indices clamped), so the load count is static and the first use
@@ -312,8 +327,8 @@ struct ProRegs {
     float x[NP][16];
     float w[NORM ? NP : 1][16];
 };
-template <bool NORM, int NP, int NT = kMVThreads>
-__device__ __forceinline__ void mv_prologue_issue(const MVArgs& A, ProRegs<NORM, NP>& R) {
+template <bool NORM, int NP, int NT = kMVThreads, class MA>  // MA: MVArgs or MVLead
+__device__ __forceinline__ void mv_prologue_issue(const MA& A, ProRegs<NORM, NP>& R) {
     const int nsub = A.cols / 16;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
@@ -415,8 +430,8 @@ template <int NI>
 struct ImgRegs {
     u32x4 v[NI];
 };
-template <int NI, int NT = kMVThreads>
-__device__ __forceinline__ void mv_img_issue(const MVArgs& A, ImgRegs<NI>& R) {
+template <int NI, int NT = kMVThreads, class MA>
+__device__ __forceinline__ void mv_img_issue(const MA& A, ImgRegs<NI>& R) {
     const int n16 = (A.cols >> 8) * (kRec / 16);
 #pragma unroll
     for (int i = 0; i < NI; ++i) R.v[i] = *(const u32x4*)(A.xq + 16 * min((int)threadIdx.x + i * NT, n16 - 1));
@@ -1048,7 +1063,8 @@ __device__ __forceinline__ float x86_silu(float x) { return x / (1.0f + x86_v_ex
 struct TaskGeo {
     int lr, R, nj, U;
 };
-__host__ __device__ inline TaskGeo task_geo(const MVArgs& A) {
+template <class MA>  // MVArgs or MVLead
+__host__ __device__ inline TaskGeo task_geo(const MA& A) {
     TaskGeo g;
     g.lr = A.lr;
     g.R = A.rpt;
@@ -1397,7 +1413,8 @@ __device__ __forceinline__ void task_any(const MA& A, const Lds& L, float* F, co
 // Q4_K and Q6_K (the types of the single-round launches of the flagship); Q5_K stays unsplit.
 // ----------------------------------------------------------------------------------
 // geometry of a split group: `lanes` lanes per row, two per unit, R rows per task
-__host__ __device__ inline TaskGeo task_geo_split(const MVArgs& A, int lanes, int R) {
+template <class MA>
+__host__ __device__ inline TaskGeo task_geo_split(const MA& A, int lanes, int R) {
     TaskGeo g;
     g.lr = lanes >> 1;
     g.R = R;

@@ -53,11 +53,11 @@ static int g_split_by_pairs = getenv("LLMI_SPLIT_BY_PAIRS") ? atoi(getenv("LLMI_
 // is unit slot k of the task, each lane holds half a unit (HalfW) and the even one stores the
 // terms; every task of the range is of type T (the launcher checks).
 template <int ACT, bool NORM, int EPI, int T, int NP, int NT = kMVThreads, int X86 = 0, int US = 1>
-__device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds& L, float* F, const TaskGeo& g, int t0,
-                                                      int G, int tbeg, int tend) {
+__device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const MVLead& E, const Lds& L, float* F,
+                                                      const TaskGeo& g, int t0, int G, int tbeg, int tend) {
     using W = std::conditional_t<US == 2, HalfW<US == 2 ? T : T_Q4_K>, UnitW<T>>;
     int pos = 0;
-    if constexpr (EPI == EPI_QKV) pos = A.st->pos;
+    if constexpr (EPI == EPI_QKV) pos = E.st->pos;
     unsigned long long best = 0;
     const int lane = threadIdx.x & 63;
     const int S = EPI == EPI_SWIGLU ? 2 * g.nj : g.nj;
@@ -74,9 +74,9 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds
     [[maybe_unused]] int nsub_done = 0, nsub_alt = 0;
     ProRegs<NORM, NP> R;
     ImgRegs<2 * NP + 1> RI;
-    const bool img = A.xq != nullptr;
-    if (img) mv_img_issue<2 * NP + 1, NT>(A, RI);  // activation loads first ...
-    else mv_prologue_issue<NORM, NP, NT>(A, R);
+    const bool img = E.xq != nullptr;
+    if (img) mv_img_issue<2 * NP + 1, NT>(E, RI);  // activation loads first (addresses: the preloaded arguments) ...
+    else mv_prologue_issue<NORM, NP, NT>(E, R);
     // Single-round launches (every wave owns at most one task: QKV, attn_output) issue
     // their weights only once the activation has arrived: the activation loads then do
     // not queue behind the chip-wide weight burst, and the weight latency overlaps the
@@ -97,7 +97,7 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds
     // Q6_K: the masked activation copies (mv_device.h q6_masks_build), after the fold buffers
     [[maybe_unused]] uint8_t* q6m = nullptr;
     if constexpr (T == T_Q6_K && kQ6Masked && !X86) {
-        q6m = (uint8_t*)L.act + fold_off(ACT, A.cols, NT / 64) + (size_t)(NT / 64) * kFoldFloats * 4;
+        q6m = (uint8_t*)L.act + fold_off(ACT, E.cols, NT / 64) + (size_t)(NT / 64) * kFoldFloats * 4;
         q6_masks_build<NT>(L, g.U, q6m);
         __syncthreads();
     }
@@ -192,40 +192,49 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const Lds
     return best;
 }
 
+// The leading arguments of k_matvec / k_matvec_split, preloaded into SGPRs (MVLead, mv_device.h)
+// (lr and rpt share a dword, lr | rpt << 16, which leaves one for the grid's workgroup count:
+// gridDim.x comes from the hidden arguments behind the struct, a fetch of its own)
+#define LLMI_MV_LEAD_PARAMS                                                                                        \
+    const float *x_, const float *nw_, const uint8_t *xq_, StepState *st_, int cols_, int ntasks_, int split_wgs_, \
+        int split_tasks_, int lr_rpt_, int nwg_
+#define LLMI_MV_LEAD MVLead { x_, nw_, xq_, st_, cols_, ntasks_, split_wgs_, split_tasks_, lr_rpt_ & 0xffff, lr_rpt_ >> 16, nwg_ }
+
 // A launch whose segments form two type groups (QKV with a Q6_K or Q5_K attn_v) is
 // split by workgroup: workgroups [0, split_wgs) run the tasks of type T, the rest the
 // tasks of type T2, each group pipelined in its own type (no divergence in a workgroup).
 template <int ACT, bool NORM, int EPI, int T, int NP, int T2 = T, int NT = kMVThreads, int X86 = 0>
-__global__ __launch_bounds__(NT) void k_matvec(MVArgs A) {
+__global__ __launch_bounds__(NT) void k_matvec(LLMI_MV_LEAD_PARAMS, MVArgs A) {
+    const MVLead E = LLMI_MV_LEAD;
     constexpr int NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const Lds L = carve(smem, ACT, A.cols);
+    const Lds L = carve(smem, ACT, E.cols);
     const int wave = uniform((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
-    float* F = (float*)(smem + fold_off(ACT, A.cols, NW)) + wave * fold_stride(ACT, X86, A.rpt, A.lr);
+    float* F = (float*)(smem + fold_off(ACT, E.cols, NW)) + wave * fold_stride(ACT, X86, E.rpt, E.lr);
     unsigned long long best;
     if constexpr (T2 == T) {
         // single type: optionally two task ranges, the larger one for the first dispatch
         // round of workgroups (mv_launch: the older of two co-resident workgroups wins
         // VALU arbitration and runs ~20 % faster per sub-item); one call site either way
-        int t0 = blockIdx.x * NW + wave, G = gridDim.x * NW, tb = 0, te = A.ntasks;
-        if (A.split_wgs > 0) {
-            if ((int)blockIdx.x < A.split_wgs) {
-                G = A.split_wgs * NW;
-                te = A.split_tasks;
+        int t0 = blockIdx.x * NW + wave, G = E.nwg * NW, tb = 0, te = E.ntasks;
+        if (E.split_wgs > 0) {
+            if ((int)blockIdx.x < E.split_wgs) {
+                G = E.split_wgs * NW;
+                te = E.split_tasks;
             } else {
-                t0 = A.split_tasks + (blockIdx.x - A.split_wgs) * NW + wave;
-                G = (gridDim.x - A.split_wgs) * NW;
-                tb = A.split_tasks;
+                t0 = E.split_tasks + (blockIdx.x - E.split_wgs) * NW + wave;
+                G = (E.nwg - E.split_wgs) * NW;
+                tb = E.split_tasks;
             }
         }
-        best = mv_body<ACT, NORM, EPI, T, NP, NT, X86>(A, L, F, task_geo(A), t0, G, tb, te);
+        best = mv_body<ACT, NORM, EPI, T, NP, NT, X86>(A, E, L, F, task_geo(E), t0, G, tb, te);
     } else {
-        if ((int)blockIdx.x < A.split_wgs)
-            best = mv_body<ACT, NORM, EPI, T, NP, NT, X86>(A, L, F, task_geo(A), blockIdx.x * NW + wave, A.split_wgs * NW, 0, A.split_tasks);
+        if ((int)blockIdx.x < E.split_wgs)
+            best = mv_body<ACT, NORM, EPI, T, NP, NT, X86>(A, E, L, F, task_geo(E), blockIdx.x * NW + wave, E.split_wgs * NW, 0, E.split_tasks);
         else
-            best = mv_body<ACT, NORM, EPI, T2, NP, NT, X86>(A, L, F, task_geo(A), A.split_tasks + (blockIdx.x - A.split_wgs) * NW + wave,
-                                                            (gridDim.x - A.split_wgs) * NW, A.split_tasks, A.ntasks);
+            best = mv_body<ACT, NORM, EPI, T2, NP, NT, X86>(A, E, L, F, task_geo(E), E.split_tasks + (blockIdx.x - E.split_wgs) * NW + wave,
+                                                            (E.nwg - E.split_wgs) * NW, E.split_tasks, E.ntasks);
     }
     if constexpr (EPI == EPI_LOGITS) {
         // workgroup max of the lanes' keys, then one atomic into this workgroup's slot
@@ -243,6 +252,13 @@ __global__ __launch_bounds__(NT) void k_matvec(MVArgs A) {
             if (blockIdx.x == 0) A.st->pos_next = cur_pos + 1;
         }
     }
+}
+
+// k_matvec / k_matvec_split launch: the leading arguments are copies of a's fields (MVLead)
+template <typename K>
+static void mv_launch_k(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const MVArgs& a) {
+    launch_k(kernel, grid, block, lds, s, true, true, a.x, a.nw, a.xq, a.st, a.cols, a.ntasks, a.split_wgs, a.split_tasks,
+             a.lr | a.rpt << 16, (int)grid.x, a);
 }
 
 // Grid of a matvec launch: never more workgroups than can be resident at once (the
@@ -316,7 +332,7 @@ static hipError_t mv_launch_wide(const MVArgs& a, hipStream_t s) {
     const size_t lds = mv_lds_total(ACT, a.cols, NW, T, T, X86);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int blocks = std::max(1, std::min(cu_count(), (a.ntasks + NW - 1) / NW));
-    launch_k(k_matvec<ACT, NORM, EPI, T, NP, T, kMVWide, X86>, dim3(blocks), dim3(kMVWide), lds, s, true, true, a);
+    mv_launch_k(k_matvec<ACT, NORM, EPI, T, NP, T, kMVWide, X86>, dim3(blocks), dim3(kMVWide), lds, s, a);
     return hipGetLastError();
 }
 template <int ACT, bool NORM, int T, int EPI, int X86>
@@ -359,7 +375,7 @@ static hipError_t mv_launch_narrow(const MVArgs& a0, hipStream_t s) {
     const dim3 g = resident_grid(k, dim3(a0.ntasks), lds, kMVNarrow);
     MVArgs a = a0;
     a.split_wgs = 0;
-    launch_k(k, g, dim3(kMVNarrow), lds, s, true, true, a);
+    mv_launch_k(k, g, dim3(kMVNarrow), lds, s, a);
     return hipGetLastError();
 }
 template <int ACT, bool NORM, int T, int EPI, int X86>
@@ -393,7 +409,7 @@ static hipError_t mv_launch(const MVArgs& a0, dim3 grid, size_t lds_in, hipStrea
         a.split_wgs = cus;
         a.split_tasks = (int)(a.ntasks * (sh / (1.0 + sh)) + 0.5);
     }
-    launch_k(k, g, dim3(kMVThreads), lds, s, true, true, a);
+    mv_launch_k(k, g, dim3(kMVThreads), lds, s, a);
     return hipGetLastError();
 }
 
@@ -428,7 +444,7 @@ static hipError_t mv_launch2(const MVArgs& a0, int split_tasks, dim3 grid, size_
                           (double)tensor_bytes(T2, a.rpt, a.cols));
     }
     a.split_wgs = w1;
-    launch_k(k, g, dim3(kMVThreads), lds, s, true, true, a);
+    mv_launch_k(k, g, dim3(kMVThreads), lds, s, a);
     return hipGetLastError();
 }
 
@@ -489,28 +505,29 @@ hipError_t mv_qkv2_launch(const MVArgs& a, int split_tasks, dim3 grid, size_t ld
 // measured the same: profiles/mv_split.)
 // ----------------------------------------------------------------------------------
 template <bool NORM, int EPI, int T, int T2, int NT, int X86, int US, int US2>
-__global__ __launch_bounds__(NT) void k_matvec_split(MVArgs A) {
+__global__ __launch_bounds__(NT) void k_matvec_split(LLMI_MV_LEAD_PARAMS, MVArgs A) {
+    const MVLead E = LLMI_MV_LEAD;
     constexpr int NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const Lds L = carve(smem, 0, A.cols);
+    const Lds L = carve(smem, 0, E.cols);
     const int wave = uniform((int)(threadIdx.x >> 6));
-    float* F = (float*)(smem + fold_off(0, A.cols, NW)) + wave * fold_stride(0, X86, 1, 4);
+    float* F = (float*)(smem + fold_off(0, E.cols, NW)) + wave * fold_stride(0, X86, 1, 4);
     if constexpr (T2 == T) {
         static_assert(US == 2 && US2 == 2, "single-type split launches split every unit");
-        mv_body<0, NORM, EPI, T, 1, NT, X86, 2>(A, L, F, task_geo_split(A, A.lr, A.rpt), blockIdx.x * NW + wave,
-                                                 gridDim.x * NW, 0, A.ntasks);
+        mv_body<0, NORM, EPI, T, 1, NT, X86, 2>(A, E, L, F, task_geo_split(E, E.lr, E.rpt), blockIdx.x * NW + wave,
+                                                 E.nwg * NW, 0, E.ntasks);
     } else {
-        if ((int)blockIdx.x < A.split_wgs) {
-            const TaskGeo g = US == 2 ? task_geo_split(A, A.lr, A.rpt) : task_geo(A);
-            mv_body<0, NORM, EPI, T, 1, NT, X86, US>(A, L, F, g, blockIdx.x * NW + wave, A.split_wgs * NW, 0, A.split_tasks);
+        if ((int)blockIdx.x < E.split_wgs) {
+            const TaskGeo g = US == 2 ? task_geo_split(E, E.lr, E.rpt) : task_geo(E);
+            mv_body<0, NORM, EPI, T, 1, NT, X86, US>(A, E, L, F, g, blockIdx.x * NW + wave, E.split_wgs * NW, 0, E.split_tasks);
         } else {
-            const int bi = (int)blockIdx.x - A.split_wgs, nb2 = (int)gridDim.x - A.split_wgs;
-            TaskGeo g = task_geo_split(A, A.lr2, A.rpt2);
+            const int bi = (int)blockIdx.x - E.split_wgs, nb2 = E.nwg - E.split_wgs;
+            TaskGeo g = task_geo_split(E, A.lr2, A.rpt2);
             if constexpr (US2 == 1) {
                 g.lr = A.lr2;
                 g.nj = (g.U + g.lr - 1) / g.lr;
             }
-            mv_body<0, NORM, EPI, T2, 1, NT, X86, US2>(A, L, F, g, A.t2beg + bi * NW + wave, nb2 * NW, A.t2beg, A.t2end);
+            mv_body<0, NORM, EPI, T2, 1, NT, X86, US2>(A, E, L, F, g, A.t2beg + bi * NW + wave, nb2 * NW, A.t2beg, A.t2end);
         }
     }
 }
@@ -522,7 +539,7 @@ static hipError_t mv_split_launch_nt(const MVArgs& a, hipStream_t s) {
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     auto k = k_matvec_split<NORM, EPI, T, T, NT, X86, 2, 2>;
     const dim3 g = resident_grid(k, dim3((a.ntasks + NW - 1) / NW), lds, NT);
-    launch_k(k, g, dim3(NT), lds, s, true, true, a);
+    mv_launch_k(k, g, dim3(NT), lds, s, a);
     return hipGetLastError();
 }
 template <bool NORM, int T, int X86>
@@ -564,7 +581,7 @@ static hipError_t mv_split_qkv2_launch_nt(const MVArgs& a0, hipStream_t s) {
     // (a wave's time goes with its instructions here, not its bytes: a Q6_K half unit costs
     // about what a whole Q4_K unit does, a Q4_K half unit half of it)
     a.split_wgs = split_groups_nw((int)g.x, NW, p1, p2, US == 2 ? 1.0 : 2.0, 2.4);
-    launch_k(k, g, dim3(NT), lds, s, true, true, a);
+    mv_launch_k(k, g, dim3(NT), lds, s, a);
     return hipGetLastError();
 }
 template <int X86, int US>
