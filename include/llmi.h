@@ -571,11 +571,21 @@ int32_t llmi_battention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int
  * positions 0..pos0+t) over one layer's caches in the step's layout (as llmi_attention);
  * out f32 [T][n_head*head_dim].  mode 0: the tiled FP64-MFMA kernel (k_pf_fa), 1: the
  * grouped LDS kernel, 2: one head per workgroup.  scratch_bytes > 0 bounds k_pf_fa's
- * score scratch (so the launch is chunked), <= 0 takes the engine's size.  Returns
- * elapsed device microseconds (>= 0) or < 0 on error. */
+ * score scratch (so the launch is chunked), <= 0 takes the engine's size.  pos0 + T <=
+ * n_ctx in mode 0 (the engine's rule wherever k_pf_fa's scratch exists), <= 32768 in modes
+ * 1 and 2 (the LDS score rows).  Returns elapsed device microseconds (>= 0) or < 0 on
+ * error. */
 double llmi_pf_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
                          const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode,
                          int64_t scratch_bytes);
+/* What llmi_pf_attention launches in mode 1 or 2 for max_kv = pos0 + T score positions: 8,
+ * 4 or 2 = k_pf_attn_g over that many query heads per workgroup (the whole GQA group while
+ * its scores fit in LDS, else a 4- or 2-head sub-group), 1 = k_pf_attn (one head per
+ * workgroup), -1 = refused (past 32768 positions).  The ceilings follow the compiled
+ * kernels' static LDS, so this asks the device (without one, a fixed allowance).  -2 for
+ * bad arguments (head shape, max_kv <= 0, a mode other than 1 or 2), before any device
+ * call. */
+int32_t llmi_pf_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t max_kv, int32_t mode);
 /* One batched-prefill attention in the flash-attention numerics (k_pf_attn_fa, what
  * prefill_enqueue launches for a LLMI_NUMERICS_FA model under LLMI_FA_PREFILL=1):
  * arguments and layouts as llmi_pf_attention, the dot association from this thread's

@@ -1012,8 +1012,10 @@ static bool pf_attention_args_ok(int n_head, int n_head_kv, int head_dim, int T,
 double llmi_pf_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
                          const float* q, const uint16_t* kc, const uint16_t* vc, float* out, int32_t mode,
                          int64_t scratch_bytes) {
-    if (!pf_attention_args_ok(n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out) || pos0 + T > kPfAttnMaxKV ||
-        mode < 0 || mode > 2) {
+    // mode 0 runs to n_ctx, the rule prefill_max_kv applies when k_pf_fa's scratch exists
+    // (pf_attention_args_ok); the LDS kernels' score rows end at kPfAttnMaxKV
+    if (!pf_attention_args_ok(n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out) || mode < 0 || mode > 2 ||
+        (mode != 0 && pos0 + T > kPfAttnMaxKV)) {
         set_err("llmi_pf_attention: bad arguments");
         return -1;
     }
@@ -1029,6 +1031,18 @@ double llmi_pf_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, in
         at.wsc_bytes = bytes;
     }
     return pf_attention_run("llmi_pf_attention", at, n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out, mode);
+    API_CATCH(-5)
+}
+
+// The kernel launch_pf_attn takes in an LDS mode at max_kv score positions (the ladder's
+// ceilings come from each kernel's static LDS: a device query, cached).
+int32_t llmi_pf_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t max_kv, int32_t mode) {
+    if (!head_shape_ok(n_head, n_head_kv, head_dim) || max_kv <= 0 || mode < 1 || mode > 2) {
+        set_err("llmi_pf_attn_path: bad arguments");
+        return -2;
+    }
+    API_TRY
+    return pf_attn_path(n_head, n_head_kv, head_dim, max_kv, mode);
     API_CATCH(-5)
 }
 

@@ -243,6 +243,9 @@ hipError_t launch_pf_gemm(const PfGemm& g, int epi, hipStream_t s);
 // short: never a silent fallback), 1 the LDS kernels (grouped, then one head per
 // workgroup), 2 one head per workgroup
 hipError_t launch_pf_attn(const PfAttn& a, int n_head, int head_dim, int T, hipStream_t s, int path = -1);
+// the kernel launch_pf_attn takes for LDS path 1 or 2 at max_kv score positions: 8, 4, 2 =
+// k_pf_attn_g over that many heads (the GQA group or a sub-group), 1 = k_pf_attn, -1 = refused
+int pf_attn_path(int n_head, int n_head_kv, int head_dim, int max_kv, int path);
 
 // activation kind of a weight type: 0 = block_q8_K (K-quants), 1 = block_q8_0
 __host__ __device__ inline int act_kind(int t) { return t == T_Q8_0 ? 1 : 0; }

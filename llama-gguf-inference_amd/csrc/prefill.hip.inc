@@ -1267,46 +1267,60 @@ static hipError_t pf_attn_g_launch(const PfAttn& a, int n_head, int T, hipStream
     return hipGetLastError();
 }
 
+// size of k_pf_attn's dynamic LDS: the scores of one head, the reduction slots, the PV partials
+static size_t pf_attn_lds(int max_kv) {
+    const size_t lds = (((size_t)max_kv * 4 + 16 + 7) & ~(size_t)7) + 8 * sizeof(double), pv = (size_t)256 * sizeof(double);
+    return lds < pv ? pv : lds;
+}
+
+// What launch_pf_attn launches for an LDS path (1: grouped, then one head per workgroup; 2:
+// one head per workgroup) at max_kv score positions: 8, 4 or 2 = k_pf_attn_g<D, that many
+// heads> (the whole GQA group, or a sub-group of it), 1 = k_pf_attn, -1 = refused
+int pf_attn_path(int n_head, int n_head_kv, int head_dim, int max_kv, int path) {
+    if ((head_dim != 128 && head_dim != 64) || n_head <= 0 || n_head_kv <= 0 || n_head % n_head_kv || max_kv <= 0) return -1;
+    const int gqa = n_head / n_head_kv;
+    auto fits = [&](int G) {
+        if (head_dim == 128) return G == 8 ? pf_attn_g_fits<128, 8>(max_kv) : G == 4 ? pf_attn_g_fits<128, 4>(max_kv) : pf_attn_g_fits<128, 2>(max_kv);
+        return G == 8 ? pf_attn_g_fits<64, 8>(max_kv) : G == 4 ? pf_attn_g_fits<64, 4>(max_kv) : pf_attn_g_fits<64, 2>(max_kv);
+    };
+    // grouped kernel while the G heads' scores fit in LDS (8B, G = 4: 10 Ki positions)
+    if (path != 2) {
+        if ((gqa == 8 || gqa == 4 || gqa == 2) && fits(gqa)) return gqa;
+        // the whole group's scores do not fit: sub-groups of 4 or 2 heads (K and V read
+        // gqa / 4 or gqa / 2 times instead of gqa times by the one-head kernel below)
+        if (gqa == 8 && fits(4)) return 4;
+        if (gqa % 2 == 0 && gqa > 2 && fits(2)) return 2;
+    }
+    if (max_kv > kPfAttnMaxKV) return -1;
+    auto k = head_dim == 128 ? k_pf_attn<128> : k_pf_attn<64>;
+    if (pf_attn_lds(max_kv) + static_lds((const void*)k) > kLdsPerCU) return -1;
+    return 1;
+}
+
 hipError_t launch_pf_attn(const PfAttn& a, int n_head, int head_dim, int T, hipStream_t s, int path) {
     if (head_dim != 128 && head_dim != 64) return hipErrorInvalidValue;
     if (a.fa) return launch_pf_attn_fa(a, n_head, head_dim, T, s);
     if (a.num) return launch_pf_attn_x86(a, n_head, n_head / a.gqa, head_dim, T, s);
     if (path < 0) path = g_pf_attn_simple ? 2 : g_pf_attn_fa ? -1 : 1;
     if (path == 0) return pf_fa_dispatch(a, n_head, head_dim, T, s);
-    const bool no_g = path == 2;  // one head per workgroup
     // the tiled FP64-MFMA kernel wherever the head shape and the scratch allow
     if (path < 0) {
         const hipError_t e = pf_fa_dispatch(a, n_head, head_dim, T, s);
         if (e != hipErrorNotSupported) return e;
     }
-    // grouped kernel while the G heads' scores fit in LDS (8B, G = 4: 10 Ki positions)
-    if (!no_g && a.pos0 + T <= a.max_kv) {
-        if (head_dim == 128 && a.gqa == 4 && pf_attn_g_fits<128, 4>(a.max_kv)) return pf_attn_g_launch<128, 4>(a, n_head, T, s);
-        if (head_dim == 128 && a.gqa == 8 && pf_attn_g_fits<128, 8>(a.max_kv)) return pf_attn_g_launch<128, 8>(a, n_head, T, s);
-        if (head_dim == 128 && a.gqa == 2 && pf_attn_g_fits<128, 2>(a.max_kv)) return pf_attn_g_launch<128, 2>(a, n_head, T, s);
-        if (head_dim == 64 && a.gqa == 8 && pf_attn_g_fits<64, 8>(a.max_kv)) return pf_attn_g_launch<64, 8>(a, n_head, T, s);
-        if (head_dim == 64 && a.gqa == 2 && pf_attn_g_fits<64, 2>(a.max_kv)) return pf_attn_g_launch<64, 2>(a, n_head, T, s);
-        if (head_dim == 64 && a.gqa == 4 && pf_attn_g_fits<64, 4>(a.max_kv)) return pf_attn_g_launch<64, 4>(a, n_head, T, s);
-        // the whole group's scores do not fit: sub-groups of 4 or 2 heads (K and V read
-        // gqa / 4 or gqa / 2 times instead of gqa times by the one-head kernel below)
-        if (a.gqa == 8) {
-            if (head_dim == 128 && pf_attn_g_fits<128, 4>(a.max_kv)) return pf_attn_g_launch<128, 4>(a, n_head, T, s);
-            if (head_dim == 64 && pf_attn_g_fits<64, 4>(a.max_kv)) return pf_attn_g_launch<64, 4>(a, n_head, T, s);
-        }
-        if (a.gqa % 2 == 0 && a.gqa > 2) {
-            if (head_dim == 128 && pf_attn_g_fits<128, 2>(a.max_kv)) return pf_attn_g_launch<128, 2>(a, n_head, T, s);
-            if (head_dim == 64 && pf_attn_g_fits<64, 2>(a.max_kv)) return pf_attn_g_launch<64, 2>(a, n_head, T, s);
-        }
-    }
-    if (a.max_kv > kPfAttnMaxKV || a.pos0 + T > a.max_kv) return hipErrorInvalidValue;
-    size_t lds = (((size_t)a.max_kv * 4 + 16 + 7) & ~(size_t)7) + 8 * sizeof(double);
-    const size_t pv = (size_t)256 * sizeof(double);
-    if (lds < pv) lds = pv;
+    if (a.gqa <= 0 || n_head % a.gqa || a.pos0 + T > a.max_kv) return hipErrorInvalidValue;
     // gfx950 launches take up to 160 KiB of dynamic LDS as is (the split decode attention
     // uses 128 KiB); hipFuncSetAttribute(MaxDynamicSharedMemorySize) is refused here with
     // "invalid argument", which failed every 8B prompt reaching past 4 Ki positions
-    auto k = head_dim == 128 ? k_pf_attn<128> : k_pf_attn<64>;
-    if (lds + static_lds((const void*)k) > kLdsPerCU) return hipErrorInvalidValue;
-    launch_k(k, dim3(n_head, T), dim3(256), lds, s, true, true, a);
+    const bool d128 = head_dim == 128;
+    switch (pf_attn_path(n_head, n_head / a.gqa, head_dim, a.max_kv, path == 2 ? 2 : 1)) {
+        case 8: return d128 ? pf_attn_g_launch<128, 8>(a, n_head, T, s) : pf_attn_g_launch<64, 8>(a, n_head, T, s);
+        case 4: return d128 ? pf_attn_g_launch<128, 4>(a, n_head, T, s) : pf_attn_g_launch<64, 4>(a, n_head, T, s);
+        case 2: return d128 ? pf_attn_g_launch<128, 2>(a, n_head, T, s) : pf_attn_g_launch<64, 2>(a, n_head, T, s);
+        case 1: break;
+        default: return hipErrorInvalidValue;
+    }
+    auto k = d128 ? k_pf_attn<128> : k_pf_attn<64>;
+    launch_k(k, dim3(n_head, T), dim3(256), pf_attn_lds(a.max_kv), s, true, true, a);
     return hipGetLastError();
 }

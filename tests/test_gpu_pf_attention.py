@@ -13,6 +13,12 @@ token counts (not a multiple of the 64 / G tokens of a tile), prompts starting m
 (pos0 > 0, key tiles with partly live rows), and a scratch bound that forces one query
 tile per launch.  Stale cache contents past the last live position are NaN here, so a
 kernel that lets them meet a zero probability fails.
+
+These are the first, random-shape cases.  The matrix on the kernels' own loop edges (key
+tiles, token counts, chunks, the exp's ranges, the LDS ladder and its ceilings, past 32768
+positions) is tests/test_gpu_pf_attention_edges.py; its inputs and the restatement used
+here (expf_np, ref_pf_attention) live in tests/pf_attention_cases.py and are proven on the
+CPU by tests/test_pf_attention_inputs.py.
 """
 from __future__ import annotations
 
@@ -21,61 +27,9 @@ import pytest
 
 import llmi
 import pyoracle as po
+from pf_attention_cases import F32, _f16, expf_np, ref_pf_attention  # noqa: F401 (test_gpu_attention imports them from here)
 
 pytestmark = pytest.mark.gpu
-
-F32 = np.float32
-
-
-def expf_np(x: np.ndarray) -> np.ndarray:
-    """include/llmi_math.h llmi_expf, vectorized (float32 ops, one rounding each)."""
-    x = np.asarray(x, F32)
-    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
-        t = x * F32(1.44269502162933349609375)
-        nf = (t + F32(12582912.0)) - F32(12582912.0)
-        n = np.where(np.isfinite(nf), nf, 0).astype(np.int64)
-        r = x - nf * F32(0.693359375)
-        r = r - nf * F32(-2.12194440e-4)
-        p = np.full_like(x, F32(1.98412698e-4))
-        for c in (1.38888889e-3, 8.33333333e-3, 4.16666667e-2, 1.66666667e-1, 0.5, 1.0, 1.0):
-            p = p * r + F32(c)
-        big = n > 127
-        p = np.where(big, p * F32(2.0), p)
-        n = np.where(big, n - 1, n)
-        small = n < -126
-        nn = np.where(small, n + 126 + 127, n + 127).clip(0, 255).astype(np.uint32)
-        sc = (nn << np.uint32(23)).view(F32)
-        out = np.where(small, (p * sc) * F32(1.17549435e-38), p * sc)
-        out = np.where(x < F32(-103.97208404541015625), F32(0.0), out)
-        out = np.where(x > F32(88.72283935546875), F32(np.inf), out)
-        out = np.where(np.isnan(x), x, out)
-    return out.astype(F32)
-
-
-def _f16(a):
-    return np.asarray(a, dtype=F32).astype(np.float16)
-
-
-def ref_pf_attention(q, K, V, pos0, G, scale):
-    """q [T][H][D] f32; K [HK][n_ctx][D] f16; V [HK][D][n_ctx] f16 -> out [T][H][D]."""
-    T, H, D = q.shape
-    nkv = pos0 + T
-    live = np.arange(nkv)[None, :] < (pos0 + np.arange(T) + 1)[:, None]  # [T][nkv]
-    out = np.empty((T, H, D), F32)
-    qf = _f16(q).astype(np.float64)
-    for h in range(H):
-        g = h // G
-        k = K[g, :nkv, :].astype(np.float64)                               # [nkv][D]
-        kq = np.cumsum(qf[:, h, None, :] * k[None, :, :], axis=2)[:, :, -1]  # [T][nkv], sequential over d
-        w = kq.astype(F32) * F32(scale)
-        mx = np.where(live, w, F32(-np.inf)).max(axis=1)
-        e = np.where(live, expf_np(w - mx[:, None]), F32(0.0))
-        s = np.cumsum(e.astype(np.float64), axis=1)[:, -1]
-        inv = (1.0 / s).astype(F32)
-        p = _f16(e * inv[:, None]).astype(np.float64)                      # [T][nkv]
-        v = V[g, :, :nkv].astype(np.float64)                               # [D][nkv]
-        out[:, h, :] = np.cumsum(p[:, None, :] * v[None, :, :], axis=2)[:, :, -1].astype(F32)
-    return out
 
 
 def _case(H, HK, D, T, pos0, seed):
