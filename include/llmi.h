@@ -83,7 +83,7 @@ struct llama_context_params {
 struct llama_batch {
     int32_t n_tokens;
     llama_token* token;
-    float* embd;           /* unsupported in llmi: must be NULL */
+    float* embd;           /* embedding INPUT: unsupported in llmi, must be NULL */
     llama_pos* pos;        /* NULL: consecutive positions after the context's last token */
     int32_t* n_seq_id;
     llama_seq_id** seq_id;
@@ -124,6 +124,48 @@ int llama_eval(struct llama_context* ctx, llama_token* tokens, int32_t n_tokens,
  * or -1 for the last one.  NULL (and llmi_last_error) if i had no logits. */
 float* llama_get_logits(struct llama_context* ctx);
 float* llama_get_logits_ith(struct llama_context* ctx, int32_t i);
+
+/* ---------- embeddings (upstream llama.h; llama-server --embeddings, POST /v1/embeddings,
+ *            docs/API_REFERENCE.md) ----------
+ * Opt-in, as upstream's.  With embeddings on, llama_decode also computes result_norm of
+ * every token's final hidden state, y = rms_norm(x) * output_norm (the vector the logits
+ * launch's fused prologue computes, the same bits), and pools the rows of each sequence's
+ * tokens IN THAT CALL, in batch order, on the device (embd.hip):
+ *   NONE  every token's row            CLS   the first token's row
+ *   LAST  the last token's row         MEAN  pooled[e] = (float) sum over t of
+ *                                            (double)(y[t][e] * (1.0f / n)), the product in
+ *                                            f32, the sum in FP64, in token order
+ *                                            (ggml's generic vec_dot_f32)
+ * RANK is refused.  Logits are as without embeddings (batch.logits decides), bit for bit.
+ * No normalisation here: that is the server's (upstream common_embd_normalize,
+ * llmi/embedding.py).  A context that never switches embeddings on runs the launches it
+ * always ran. */
+#define LLMI_POOLING_TYPE_UNSPECIFIED -1
+#define LLMI_POOLING_TYPE_NONE 0
+#define LLMI_POOLING_TYPE_MEAN 1
+#define LLMI_POOLING_TYPE_CLS 2
+#define LLMI_POOLING_TYPE_LAST 3
+#define LLMI_POOLING_TYPE_RANK 4
+/* upstream llama_set_embeddings.  Off by default; switching off drops the last results. */
+void llama_set_embeddings(struct llama_context* ctx, bool embeddings);
+/* upstream keeps the pooling type in llama_context_params; llmi's struct is laid out by its
+ * callers, so it is a setter.  The default is the model's GGUF <arch>.pooling_type if that
+ * is one of NONE..LAST, else NONE.  0 on success; -1 and llmi_last_error() naming `type`
+ * for RANK or a value that is no pooling type, or naming ctx when it is NULL. */
+int32_t llmi_set_pooling_type(struct llama_context* ctx, int32_t type);
+/* upstream llama_pooling_type: the context's; LLMI_POOLING_TYPE_UNSPECIFIED for NULL */
+int32_t llama_pooling_type(const struct llama_context* ctx);
+/* the model's GGUF <arch>.pooling_type, -1 when the key is absent (or model is NULL) */
+int32_t llmi_model_pooling_type(const struct llama_model* model);
+/* upstream llama_get_embeddings_seq: the pooled n_embd floats of seq_id from the last
+ * llama_decode.  Context-owned host memory, valid until the next decode / free.  NULL and
+ * llmi_last_error(): embeddings off, pooling NONE, no token of seq_id in that call. */
+float* llama_get_embeddings_seq(struct llama_context* ctx, llama_seq_id seq_id);
+/* upstream llama_get_embeddings_ith / llama_get_embeddings, pooling NONE only: batch token
+ * i's row (-1: the last token's) / all rows [n_tokens][n_embd] in batch order.  NULL and
+ * llmi_last_error(): embeddings off, a pooling other than NONE, i outside the batch. */
+float* llama_get_embeddings_ith(struct llama_context* ctx, int32_t i);
+float* llama_get_embeddings(struct llama_context* ctx);
 
 /* ---------- model / context introspection ---------- */
 /* owned by the model: valid on any thread until llama_model_free */
@@ -544,6 +586,19 @@ int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
 int32_t llmi_kv_seq_copy(int32_t n_planes, int32_t head_dim, int32_t n_ctx, int32_t p0, int32_t p1,
                          const uint16_t* kc_src, const uint16_t* vc_src, const int32_t* hist_src,
                          uint16_t* kc_dst, uint16_t* vc_dst, int32_t* hist_dst, double* usec);
+/* k_embd_rows / k_embd_mean alone (the embeddings launch of llama_decode) over device
+ * pointers, on the null stream, synchronised.  x_dev [n_tok][ldx] f32 holds the final hidden
+ * states of tokens t0 .. t0 + n_tok - 1 of a sequence of n_total tokens, norm_w_dev [n_embd]
+ * the output_norm weight; pooling one of LLMI_POOLING_TYPE_NONE..LAST.  acc_dev [n_embd]
+ * FP64 (MEAN; may be NULL otherwise) is started from zero by the call with t0 == 0 and
+ * carried by the others.  out_dev is [n_tok][n_embd] for NONE, else [n_embd], written when
+ * the chunk holds the deciding token(s): every row for NONE, t0 == 0 for CLS, t0 + n_tok ==
+ * n_total for LAST and MEAN; nothing else is written.  usec (optional): the launches'
+ * event-timed device microseconds.  < 0 before any device call, llmi_last_error() naming the
+ * argument: a null pointer, n_embd no positive multiple of 256, ldx < n_embd, n_tok <= 0,
+ * t0 < 0, t0 + n_tok > n_total, pooling outside 0..3.  0 on success. */
+int32_t llmi_embd_pool(const float* x_dev, int64_t ldx, int32_t n_tok, int32_t n_embd, const float* norm_w_dev, float eps,
+                       int32_t pooling, int32_t n_total, int32_t t0, double* acc_dev, float* out_dev, double* usec);
 /* The path launch_attention takes for this head shape at the KV bound kv_bound (a multiple
  * of 256 in the engine) under `mode` (0 auto, 1..7 forced, LLMI_ATTN_MODE's numbering): 1
  * fused, 2 split, 3 two-kernel, 4 exchange, 5 register-prefetched, 6 dim-split, 7

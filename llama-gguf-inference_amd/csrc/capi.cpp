@@ -260,6 +260,9 @@ struct llama_context* llama_init_from_model(struct llama_model* model, struct ll
         delete ctx;
         return nullptr;
     }
+    // upstream's default pooling: the model's own (GGUF <arch>.pooling_type) if it is one llmi runs
+    const int mp = model->m.hp.pooling_type;
+    ctx->c.pooling = mp >= POOLING_NONE && mp <= POOLING_LAST ? mp : POOLING_NONE;
     return ctx;
     API_CATCH(nullptr)
 }
@@ -322,11 +325,15 @@ static void copy_out(llama_context* ctx, int r, const float* logits_dev, const S
 // at least the last token to a decode step), then decode steps.
 // LLMI_NO_PREFILL=1 runs every token as a decode step (and so does a flash-attention
 // numerics model without LLMI_FA_PREFILL=1: prefill_supported).
+// embd_dst non-null (embeddings mode): the sequence's final hidden states are pooled as they
+// appear, each prefill chunk inside prefill_enqueue and each decode step here.
 static bool run_seq(llama_context* ctx, const llama_batch& batch, int seq, const std::vector<int>& idx,
-                    const std::vector<int>& pos, const std::vector<int>& rows, double& bytes, std::string& err) {
+                    const std::vector<int>& pos, const std::vector<int>& rows, double& bytes, std::string& err,
+                    float* embd_dst = nullptr) {
     Context& c = ctx->c;
     context_select_seq(c, seq);
     const int n = (int)idx.size();
+    if (embd_dst) embd_begin(c, n, embd_dst);
     int i0 = 0;
     const char* no_pf_env = getenv("LLMI_NO_PREFILL");
     const bool no_pf = no_pf_env && atoi(no_pf_env) != 0;
@@ -356,6 +363,7 @@ static bool run_seq(llama_context* ctx, const llama_batch& batch, int seq, const
         bytes += bytes_per_token(*c.m, p + 1);
         const int r = rows[(size_t)idx[(size_t)i]];
         if (r >= 0) copy_out(ctx, r, c.logits, c.st, p);
+        if (embd_dst && !embd_pool_enqueue(c, c.x, c.m->hp.n_embd, 1, err)) return false;
     }
     return true;
 }
@@ -398,13 +406,23 @@ int32_t llama_decode(struct llama_context* ctx, struct llama_batch batch) {
     c.logits_host.resize((size_t)std::max(1, n_out) * hp.n_vocab);
     std::string err;
     double bytes = 0;
+    // embeddings mode (llama_set_embeddings): every sequence goes through run_seq, which pools
+    // its hidden states; pooling NONE keeps a row per token, sequence by sequence
+    const bool embd = c.embd_on;
+    const size_t E = (size_t)hp.n_embd;
+    ctx->embd_call = -2;
+    struct EmbdDone {  // no sequence is being pooled once the call returns, however it returns
+        Context& c;
+        ~EmbdDone() { c.embd_total = 0; }
+    } embd_done{c};
+    if (embd && !embd_alloc(c, c.pooling == POOLING_NONE ? n : c.n_seq, err)) { set_err("llama_decode: " + err); return -2; }
     hipEventRecord(c.ev0, c.stream);
     // sequences with one token each advance together through batched steps (batch.hip,
     // up to kMaxBatch per step); the others run one sequence at a time
     std::vector<int> singles;
     for (int s = 0; s < c.n_seq; ++s)
         if (by_seq[(size_t)s].size() == 1) singles.push_back(s);
-    if (singles.size() < 2) singles.clear();
+    if (singles.size() < 2 || embd) singles.clear();
     for (size_t g = 0; g < singles.size(); g += kMaxBatch) {
         const int nt = (int)std::min<size_t>(kMaxBatch, singles.size() - g);
         const int* seqs = singles.data() + g;
@@ -431,14 +449,29 @@ int32_t llama_decode(struct llama_context* ctx, struct llama_batch batch) {
             if (r >= 0) copy_out(ctx, r, c.blogits + (size_t)k * hp.n_vocab, c.st0 + s, p);
         }
     }
+    size_t embd_row = 0;  // pooling NONE: the first row of the sequence's tokens
     for (int s = 0; s < c.n_seq; ++s) {
         if (by_seq[(size_t)s].empty() || std::find(singles.begin(), singles.end(), s) != singles.end()) continue;
-        if (!run_seq(ctx, batch, s, by_seq[(size_t)s], pos_of[(size_t)s], rows, bytes, err)) {
+        float* dst = !embd ? nullptr : c.embd_out + (c.pooling == POOLING_NONE ? embd_row : (size_t)s) * E;
+        if (!run_seq(ctx, batch, s, by_seq[(size_t)s], pos_of[(size_t)s], rows, bytes, err, dst)) {
             set_err("llama_decode: " + err);
             return -3;
         }
+        embd_row += by_seq[(size_t)s].size();
     }
     hipEventRecord(c.ev1, c.stream);
+    if (embd) {
+        if (c.pooling == POOLING_NONE) {
+            ctx->embd_stage.resize((size_t)n * E);
+            (void)hipMemcpyAsync(ctx->embd_stage.data(), c.embd_out, (size_t)n * E * 4, hipMemcpyDeviceToHost, c.stream);
+        } else {
+            ctx->embd_host.resize((size_t)c.n_seq * E);
+            for (int s = 0; s < c.n_seq; ++s)
+                if (!by_seq[(size_t)s].empty())
+                    (void)hipMemcpyAsync(ctx->embd_host.data() + (size_t)s * E, c.embd_out + (size_t)s * E, E * 4,
+                                         hipMemcpyDeviceToHost, c.stream);
+        }
+    }
     context_fault_readback(c);
     hipError_t e = hipStreamSynchronize(c.stream);
     if (e != hipSuccess) { set_err("llama_decode: " + hip_err(e)); return -4; }
@@ -447,6 +480,19 @@ int32_t llama_decode(struct llama_context* ctx, struct llama_batch batch) {
     hipEventElapsedTime(&ms, c.ev0, c.ev1);
     c.last_us = ms * 1e3;
     c.last_bytes = bytes;
+    if (embd && c.pooling == POOLING_NONE) {  // the staged rows, sequence by sequence, into batch order
+        ctx->embd_host.resize((size_t)n * E);
+        size_t r = 0;
+        for (int s = 0; s < c.n_seq; ++s)
+            for (int i : by_seq[(size_t)s])
+                std::memcpy(ctx->embd_host.data() + (size_t)i * E, ctx->embd_stage.data() + (r++) * E, E * 4);
+        ctx->embd_rows = n;
+        ctx->embd_call = POOLING_NONE;
+    } else if (embd) {
+        ctx->embd_seq_ok.assign((size_t)c.n_seq, 0);
+        for (int s = 0; s < c.n_seq; ++s) ctx->embd_seq_ok[(size_t)s] = !by_seq[(size_t)s].empty();
+        ctx->embd_call = c.pooling;
+    }
     for (int s = 0; s < c.n_seq; ++s) {
         if (by_seq[(size_t)s].empty()) continue;
         int last = seq_past_of(c, s) - 1;

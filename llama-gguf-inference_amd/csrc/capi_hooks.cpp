@@ -931,6 +931,32 @@ int32_t llmi_kv_seq_copy(int32_t n_planes, int32_t head_dim, int32_t n_ctx, int3
     API_CATCH(-5)
 }
 
+// k_embd_rows / k_embd_mean alone over the caller's device memory (the launch llama_decode
+// makes per prefill chunk and decode step in embeddings mode).  Every refusal comes before
+// the first device call, so a machine without a GPU can ask for them.
+int32_t llmi_embd_pool(const float* x_dev, int64_t ldx, int32_t n_tok, int32_t n_embd, const float* norm_w_dev, float eps,
+                       int32_t pooling, int32_t n_total, int32_t t0, double* acc_dev, float* out_dev, double* usec) {
+    API_TRY
+    const std::string who = "llmi_embd_pool: ";
+    EmbdPoolArgs a;
+    a.x = x_dev; a.ldx = ldx; a.n_tok = n_tok; a.n_embd = n_embd; a.w = norm_w_dev; a.eps = eps;
+    a.pooling = pooling; a.n_total = n_total; a.t0 = t0; a.acc = acc_dev; a.out = out_dev;
+    std::string why;
+    if (!embd_pool_ok(a, why)) { set_err(who + why); return -1; }
+    DevPool P;
+    if (pooling == POOLING_MEAN) {
+        a.scale = P.get<float>((size_t)n_tok * sizeof(float));
+        if (!a.scale) { set_err(who + hip_err(P.err)); return -2; }
+    }
+    HipObjs h;
+    auto launch = [&] { return launch_embd_pool(a, nullptr); };
+    hipError_t e = usec ? time_launch(h, launch, *usec) : launch();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_err(who + hip_err(e)); return -3; }
+    return 0;
+    API_CATCH(-5)
+}
+
 // The decode attention path launch_attention takes for this shape, KV bound and mode (host
 // only: no device call, so a test can ask on a machine without a GPU).
 int32_t llmi_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t kv_bound, int32_t mode) {

@@ -20,6 +20,12 @@ struct llama_context {
     std::vector<char> host_valid;   // per output row: logits_host filled
     unsigned long long* keys_pinned = nullptr;  // per output row argmax key (pinned host)
     int keys_cap = 0;
+    // the embeddings of the last llama_decode (capi_embd.cpp's getters), host memory
+    int embd_call = -2;             // that call's pooling type; -2: it produced no embeddings
+    int embd_rows = 0;              // pooling NONE: the call's tokens
+    std::vector<float> embd_host;   // NONE: [embd_rows][n_embd] in batch order; else [n_seq][n_embd]
+    std::vector<float> embd_stage;  // NONE: the rows as the device wrote them, sequence by sequence
+    std::vector<char> embd_seq_ok;  // pooled: the sequence had tokens in the call
 };
 
 namespace llmi {

@@ -80,7 +80,8 @@ Context::~Context() {
     for (auto& g : lgraphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : lbgraphs) (void)hipGraphExecDestroy(g.second);
     void* bufs[] = {srec, suni, lrec, lp_lse, lp_tok, lp_top, lp_top_id, lp_win_tok, lp_win_raw, x, q, att, h, logits, scores, rope, kc0, vc0, st0, hist0, pf_tok, pf_x, pf_q, pf_att, pf_h, pf_aq, pf_abs, pf_ad, pf_abf, pf_wsc,
-                    bx, bq, batt, bh, blogits, bscores, btpos, btseq, baq, babs, bad, babf, le_cnt, le_trace};
+                    bx, bq, batt, bh, blogits, bscores, btpos, btseq, baq, babs, bad, babf, le_cnt, le_trace,
+                    embd_acc, embd_scale, embd_out};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (ev0) (void)hipEventDestroy(ev0);
@@ -171,6 +172,7 @@ bool model_load(const std::string& path, int device, bool vocab_only, bool no_up
     hp.eps = (float)f.num("llama.attention.layer_norm_rms_epsilon", 1e-5);
     hp.rope_base = (float)f.num("llama.rope.freq_base", 10000.0);
     hp.file_type = (int)f.num("general.file_type", 0);
+    hp.pooling_type = (int)f.num("llama.pooling_type", -1);
     if (hp.n_embd <= 0 || hp.n_layer <= 0 || hp.n_head <= 0 || hp.n_head_kv <= 0) {
         err = "missing llama.* hyperparameters";
         return false;
@@ -1202,8 +1204,51 @@ bool prefill_enqueue(Context& c, const int32_t* tokens, int n, int pos0, std::st
             g.w = seg_of(m, L.wd, 0); g.rows = (int)L.wd.rows; g.cols = F; g.y = c.pf_x; g.ldy = E;
             PFC(launch_pf_gemm(g, EPI_ADD, c.stream));
         }
+        // embeddings: the chunk's final hidden states, before the next chunk overwrites them
+        if (c.embd_total > 0 && !embd_pool_enqueue(c, c.pf_x, E, T, err)) return false;
     }
 #undef PFC
+    return true;
+}
+
+// ---------------------------------------------------------------------------------
+// Embeddings (embd.hip): result_norm + pooling of the sequence llama_decode is running.
+// ---------------------------------------------------------------------------------
+bool embd_alloc(Context& c, int rows, std::string& err) {
+    const size_t E = (size_t)c.m->hp.n_embd;
+    if (!c.embd_acc) HIPC(hipMalloc(&c.embd_acc, E * sizeof(double)));
+    if (!c.embd_scale) HIPC(hipMalloc(&c.embd_scale, (size_t)kEmbdMaxChunk * sizeof(float)));
+    if (rows > c.embd_cap) {
+        if (c.embd_out) (void)hipFree(c.embd_out);
+        c.embd_out = nullptr;
+        c.embd_cap = 0;
+        HIPC(hipMalloc(&c.embd_out, (size_t)rows * E * sizeof(float)));
+        c.embd_cap = rows;
+    }
+    return true;
+}
+
+void embd_begin(Context& c, int n_total, float* dst) {
+    c.embd_total = n_total;
+    c.embd_done = 0;
+    c.embd_dst = dst;
+}
+
+bool embd_pool_enqueue(Context& c, const float* x, int64_t ldx, int n_tok, std::string& err) {
+    const HParams& hp = c.m->hp;
+    for (int b0 = 0; b0 < n_tok; b0 += kEmbdMaxChunk) {
+        EmbdPoolArgs a;
+        a.x = x + (size_t)b0 * ldx; a.ldx = ldx; a.n_tok = std::min(kEmbdMaxChunk, n_tok - b0); a.n_embd = hp.n_embd;
+        a.w = (const float*)(c.m->arena + c.m->out_norm.off_a); a.eps = hp.eps;
+        a.pooling = c.pooling; a.n_total = c.embd_total; a.t0 = c.embd_done;
+        a.acc = c.embd_acc; a.scale = c.embd_scale;
+        a.out = c.pooling == POOLING_NONE ? c.embd_dst + (size_t)c.embd_done * hp.n_embd : c.embd_dst;
+        std::string why;
+        if (!embd_pool_ok(a, why)) { err = "embeddings: " + why; return false; }
+        const hipError_t e = launch_embd_pool(a, c.stream);
+        if (e != hipSuccess) { err = "launch_embd_pool: " + hip_err(e); return false; }
+        c.embd_done += a.n_tok;
+    }
     return true;
 }
 

@@ -21,6 +21,7 @@ struct HParams {
     int n_embd = 0, n_layer = 0, n_head = 0, n_head_kv = 0, head_dim = 0, n_ff = 0, n_vocab = 0;
     int n_rot = 0, n_ctx_train = 0, file_type = 0;
     float eps = 1e-5f, rope_base = 10000.f;
+    int pooling_type = -1;  // GGUF <arch>.pooling_type (enum llama_pooling_type), -1 when absent
 };
 
 struct Layer {
@@ -164,6 +165,19 @@ struct Context {
     float* pf_wsc = nullptr;       // k_pf_fa score scratch (pf_fa_scratch_bytes; null: LDS attention kernels)
     size_t pf_wsc_bytes = 0;
     int64_t pf_tokens = 0;         // tokens sent through prefill_enqueue since creation (llmi_prefill_token_count)
+    // embeddings (embd.hip; llama_set_embeddings, off by default): with embd_on, llama_decode
+    // pools each sequence's final hidden states as its tokens pass -- prefill_enqueue at the
+    // end of every ubatch chunk (pf_x), run_seq after every decode step (x) -- through
+    // embd_pool_enqueue.  embd_total > 0 only while a sequence of that many tokens is
+    // being pooled: embd_done of them have passed, embd_dst is where its result goes.
+    bool embd_on = false;
+    int pooling = POOLING_NONE;
+    double* embd_acc = nullptr;    // [n_embd] the mean's FP64 sums, carried across chunks
+    float* embd_scale = nullptr;   // [kEmbdMaxChunk] the chunk's RMSNorm scales (mean)
+    float* embd_out = nullptr;     // [embd_cap][n_embd] this call's rows (NONE) or pooled vectors by sequence
+    int embd_cap = 0;
+    int embd_total = 0, embd_done = 0;
+    float* embd_dst = nullptr;
     ~Context();
 };
 
@@ -220,6 +234,13 @@ int prefill_max_kv(Context& c);
 // cache written, no logits); enqueued on c.stream, no synchronisation
 bool prefill_enqueue(Context& c, const int32_t* tokens, int n, int pos0, std::string& err);
 void context_clear(Context& c);
+// embeddings: room for `rows` result rows in c.embd_out (and the mean's scratch), allocated on first use
+constexpr int kEmbdMaxChunk = 4096;  // tokens per embd_pool_enqueue call (the largest prefill ubatch)
+bool embd_alloc(Context& c, int rows, std::string& err);
+// pool the next n_tok tokens (their final hidden states at x, rows ldx floats apart) of the
+// sequence embd_begin announced; enqueued on c.stream after the launches that wrote x
+void embd_begin(Context& c, int n_total, float* dst);
+bool embd_pool_enqueue(Context& c, const float* x, int64_t ldx, int n_tok, std::string& err);
 // enqueue the device fault word's read-back (before the call's stream sync) ...
 void context_fault_readback(Context& c);
 // ... and after the sync: false (err set, word re-armed) if an in-kernel wait gave up

@@ -474,4 +474,31 @@ bool kv_seq_cp_ok(const KvCopyArgs& a);
 // max_blocks: the context's matvec grid cap (mv_grid_cap); the grid is sized from it
 hipError_t launch_kv_seq_cp(const KvCopyArgs& a, int max_blocks, hipStream_t stream);
 
+// Embeddings on the device (embd.hip): result_norm of the final hidden states, y =
+// (x*scale)*w with the logits prologue's scale (mv_norm_scale), and upstream's pooling over
+// the tokens of one sequence (enum llama_pooling_type; RANK is not taken).  A call covers
+// tokens t0 .. t0 + n_tok - 1 of a sequence of n_total: `out` is written when the chunk
+// holds the deciding token(s) -- every row for NONE ([n_tok][n_embd]), else [n_embd] at
+// t0 == 0 (CLS) or t0 + n_tok == n_total (LAST, MEAN).  MEAN: pooled[e] = (float) sum over t
+// of (double)(y[t][e] * (1.0f / n_total)) in token order, the FP64 sum in acc [n_embd], which
+// the chunk at t0 == 0 starts from zero and every later chunk carries.
+enum : int { POOLING_UNSPECIFIED = -1, POOLING_NONE = 0, POOLING_MEAN = 1, POOLING_CLS = 2, POOLING_LAST = 3, POOLING_RANK = 4 };
+struct EmbdPoolArgs {
+    const float* x = nullptr;   // [n_tok][ldx] final hidden states
+    int64_t ldx = 0;
+    int n_tok = 0, n_embd = 0;
+    const float* w = nullptr;   // output_norm.weight [n_embd]
+    float eps = 0.f;
+    int pooling = POOLING_NONE;
+    int n_total = 0, t0 = 0;
+    double* acc = nullptr;      // MEAN: [n_embd]
+    float* scale = nullptr;     // MEAN: [n_tok] scratch (the rows' RMSNorm scales)
+    float* out = nullptr;
+};
+// n_embd a positive multiple of 256, ldx >= n_embd, n_tok >= 1, 0 <= t0, t0 + n_tok <=
+// n_total, pooling 0..3, no null pointer (acc: MEAN only); why names the argument
+bool embd_pool_ok(const EmbdPoolArgs& a, std::string& why);
+// asynchronous on `stream`; never inside a captured graph (t0, n_total vary per call)
+hipError_t launch_embd_pool(const EmbdPoolArgs& a, hipStream_t stream);
+
 }  // namespace llmi

@@ -14,6 +14,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._lib import LlmiLibraryError, last_error, lib, llama_context_params, llama_model_params  # noqa: F401
+from ._lib import (POOLING_CLS, POOLING_LAST, POOLING_MEAN, POOLING_NONE, POOLING_RANK,  # noqa: F401
+                   POOLING_UNSPECIFIED)
 
 # ggml type ids
 F32, F16, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 8, 12, 13, 14, 15
@@ -182,6 +184,11 @@ class Model:
         L.llama_model_desc(self._h, buf, 256)
         self.desc = buf.value.decode()
         self.numerics = int(L.llmi_model_numerics(self._h))
+
+    @property
+    def pooling_type(self) -> int:
+        """The GGUF's <arch>.pooling_type (llmi_model_pooling_type), -1 when absent."""
+        return int(lib().llmi_model_pooling_type(self._h))
 
     @classmethod
     def load_fanout(cls, path: str, main_gpu: int, uid: bytes, nranks: int, rank: int,
@@ -381,6 +388,22 @@ def kv_seq_copy(n_planes: int, head_dim: int, n_ctx: int, p0: int, p1: int, kc_s
     return us.value
 
 
+def embd_pool(x_dev: int, ldx: int, n_tok: int, n_embd: int, norm_w_dev: int, eps: float, pooling: int, n_total: int,
+              t0: int, acc_dev: int, out_dev: int) -> float:
+    """llmi_embd_pool: k_embd_rows / k_embd_mean alone (llama_decode's embeddings launch) over
+    device addresses: x [n_tok][ldx] f32, the final hidden states of tokens t0 .. t0 + n_tok - 1
+    of a sequence of n_total; norm_w [n_embd]; acc [n_embd] float64 (mean; 0 otherwise); out
+    [n_tok][n_embd] for POOLING_NONE, else [n_embd].  Returns the launches' event-timed device
+    microseconds; bad arguments raise before any device call."""
+    us = C.c_double()
+    vp = lambda a: C.c_void_p(int(a)) if a else None  # noqa: E731
+    r = lib().llmi_embd_pool(vp(x_dev), int(ldx), int(n_tok), int(n_embd), vp(norm_w_dev), float(eps), int(pooling),
+                             int(n_total), int(t0), vp(acc_dev), vp(out_dev), C.byref(us))
+    if r != 0:
+        raise LlmiError(f"llmi_embd_pool returned {r}: {last_error()}")
+    return us.value
+
+
 # the device's StepState (llmi_step_state) as a NumPy record
 STEP_STATE = np.dtype([("token_in", "<i4"), ("token_in_pos", "<i4"), ("pos_next", "<i4"), ("pos", "<i4"), ("token", "<i4"),
                        ("seq", "<u4"), ("key", "<u8", (2, 64))])
@@ -568,6 +591,36 @@ class Context:
             lps.append([(float(tok_lp[i, j]), [int(t) for t in top_id[i, j, :m[j]]], [float(v) for v in top_lp[i, j, :m[j]]])
                         for j in range(n)])
         return [list(out[i * n:(i + 1) * n]) for i in range(k)], lps
+
+    def set_embeddings(self, on: bool) -> None:
+        """llama_set_embeddings: while on, decode also pools the final hidden states of each
+        sequence's tokens (embeddings_seq / embeddings_ith).  Off by default."""
+        lib().llama_set_embeddings(self._h, bool(on))
+
+    def set_pooling(self, pooling: int) -> None:
+        """llmi_set_pooling_type: POOLING_NONE / MEAN / CLS / LAST (RANK is refused)."""
+        if lib().llmi_set_pooling_type(self._h, int(pooling)) != 0:
+            raise LlmiError(last_error())
+
+    @property
+    def pooling(self) -> int:
+        """llama_pooling_type: the model's GGUF default unless set_pooling changed it."""
+        return int(lib().llama_pooling_type(self._h))
+
+    def embeddings_seq(self, seq: int = 0) -> np.ndarray:
+        """llama_get_embeddings_seq: the pooled (not normalised) vector of sequence seq from the
+        last decode."""
+        p = lib().llama_get_embeddings_seq(self._h, int(seq))
+        if not p:
+            raise LlmiError(last_error())
+        return np.ctypeslib.as_array(p, shape=(self.model.n_embd,)).copy()
+
+    def embeddings_ith(self, i: int = -1) -> np.ndarray:
+        """llama_get_embeddings_ith (pooling none): batch token i's normed row, -1 the last."""
+        p = lib().llama_get_embeddings_ith(self._h, int(i))
+        if not p:
+            raise LlmiError(last_error())
+        return np.ctypeslib.as_array(p, shape=(self.model.n_embd,)).copy()
 
     def seq_rm(self, seq: int, p0: int = 0, p1: int = -1) -> bool:
         """llama_kv_self_seq_rm (tail removal)."""

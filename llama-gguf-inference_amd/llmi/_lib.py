@@ -139,6 +139,8 @@ class llmi_sampler_params(C.Structure):
 
 SAMPLE_MAX_TOP_K, SAMPLE_MAX_LAST_N = 256, 256  # LLMI_SAMPLE_MAX_*
 LOGPROBS_MAX_TOP = 20  # LLMI_LOGPROBS_MAX_TOP
+# LLMI_POOLING_TYPE_* (upstream enum llama_pooling_type)
+POOLING_UNSPECIFIED, POOLING_NONE, POOLING_MEAN, POOLING_CLS, POOLING_LAST, POOLING_RANK = -1, 0, 1, 2, 3, 4
 
 # name -> (restype, argtypes); every entry point declared in include/llmi.h
 _P = C.c_void_p
@@ -218,6 +220,15 @@ SIGNATURES = {
     "llmi_attention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32]),
     "llmi_kv_seq_copy": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P,
                                      C.POINTER(C.c_double)]),
+    "llama_set_embeddings": (None, [_P, C.c_bool]),
+    "llmi_set_pooling_type": (C.c_int32, [_P, C.c_int32]),
+    "llama_pooling_type": (C.c_int32, [_P]),
+    "llmi_model_pooling_type": (C.c_int32, [_P]),
+    "llama_get_embeddings_seq": (C.POINTER(C.c_float), [_P, C.c_int32]),
+    "llama_get_embeddings_ith": (C.POINTER(C.c_float), [_P, C.c_int32]),
+    "llama_get_embeddings": (C.POINTER(C.c_float), [_P]),
+    "llmi_embd_pool": (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_float, C.c_int32, C.c_int32, C.c_int32,
+                                   _P, _P, C.POINTER(C.c_double)]),
     "llmi_attn_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "llmi_attn_x86_form": (C.c_int32, [C.c_int32, C.c_int32]),
     "llmi_battention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _P, _P,

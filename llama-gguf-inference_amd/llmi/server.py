@@ -11,8 +11,8 @@ module answers that contract:
   GET  /v1/models              OpenAI model list
   POST /v1/completions         prompt: str | [token ids]; non-stream or SSE
   POST /v1/chat/completions    messages -> chat template -> tokens; non-stream or SSE
-  POST /v1/embeddings          501 not_supported_error (the reference starts llama-server
-                               without embedding support)
+  POST /v1/embeddings          501 not_supported_error unless started with --embeddings (the
+                               reference starts llama-server without embedding support)
   Authorization: Bearer <key> required on every route but /health when a key is
   configured (401 otherwise; llama-server's public endpoints are /health and /v1/health)
 
@@ -71,6 +71,28 @@ usage.prompt_tokens_details.cached_tokens (native /completion: tokens_cached) an
 replica's /health entry the totals prompt_tokens and cached_tokens; among equally loaded
 replicas a request goes to the one that holds the longest prefix of its prompt.
 
+Embeddings are opt-in, as llama-server's: `--embeddings` (or `--embedding`, LLMI_EMBEDDINGS=1)
+and `--pooling none|mean|cls|last` (default: the model's GGUF pooling_type, else none).  Then
+
+  POST /v1/embeddings          input: str | [str] | [token ids] | [[token ids] | str, ...]
+  POST /embeddings, /embedding the same (upstream's aliases; `content` is upstream's native
+                               spelling of `input`)
+      -> {"object":"list","data":[{"object":"embedding","embedding":[...],"index":i}],"model":...,
+          "usage":{"prompt_tokens":n,"total_tokens":n}}
+
+An input goes through its replica's scheduler thread like any request: a free sequence is
+cleared, ONE llama_decode runs the whole input from position 0 with embeddings switched on
+around that call only (the final hidden states are normed and pooled on the device as the
+prefill chunks and the last decode step pass, embd.hip), the pooled vector is read, and the
+sequence is cleared and released; its prompt-cache entry is forgotten, so embedding inputs
+neither use nor feed the prompt cache.  The vector is normalised on the host as upstream's
+common_embd_normalize does (llmi/embedding.py; `embd_normalize`: 2 Euclidean, the default, or
+-1 none; anything else is a 400); `encoding_format: "base64"` gives little-endian f32.  400
+invalid_request_error: an empty input, one longer than the context ("input is too large to
+process"), pooling none on /v1/embeddings (not OpenAI compatible; the native routes then
+return each token's row, not normalised); 500 as on the other routes when the decode fails.
+Each replica's /health entry gains embedding_requests and embedding_tokens.
+
 Text: the GGUF's own tokenizer (SPM or byte-level BPE from tokenizer.ggml.*) and chat
 template (tokenizer.chat_template, sandboxed Jinja2), llmi/tokenizer.py; streamed text
 holds incomplete UTF-8 sequences back until their last byte.
@@ -78,6 +100,7 @@ holds incomplete UTF-8 sequences back until their last byte.
 from __future__ import annotations
 
 import argparse
+import base64
 import json
 import os
 import queue
@@ -90,6 +113,7 @@ from typing import Callable, Iterable, Optional
 
 import numpy as np
 
+from .embedding import POOLING_NAMES, normalize
 from .sampling import Sampler, SamplingParams, StopFilter, device_eligible, find_stop, parse_stop, token_logprobs
 
 # a greedy slot of a sampled batched call: the chain that is an argmax of the raw logits
@@ -281,6 +305,21 @@ class Request:
         self.q.put(None)
 
 
+class EmbedRequest:
+    """One embedding input: token ids in, through `q` the pooled vector (pooling none: the
+    tokens' rows) or None with `error` set."""
+
+    def __init__(self, tokens: list[int]):
+        self.tokens = list(tokens)
+        self.q: "queue.Queue" = queue.Queue()
+        self.error: Optional[str] = None
+        self.replica = -1
+
+    def fail(self, err: str) -> None:
+        self.error = err
+        self.q.put(None)
+
+
 def _common_prefix(a: list[int], b: list[int]) -> int:
     n = min(len(a), len(b))
     if a[:n] == b[:n]:
@@ -328,6 +367,8 @@ class Replica:
         self.tick = 0
         self.prompt_tokens = 0   # prompt tokens admitted / of them served from the cache
         self.cached_tokens = 0
+        self.embedding_requests = 0  # embedding inputs served / their tokens
+        self.embedding_tokens = 0
         self.th = threading.Thread(target=self._run, name=f"llmi-replica-{idx}", daemon=True)
         self.th.start()
 
@@ -335,7 +376,7 @@ class Replica:
         with self.lock:
             return self.n_queued + len(self.active)
 
-    def submit(self, r: Request) -> None:
+    def submit(self, r) -> None:
         with self.lock:
             self.n_queued += 1
             self.requests += 1
@@ -392,8 +433,43 @@ class Replica:
         t = max(range(self.slots), key=lambda s: (lens[s], -s))
         return seq, lens[seq], t, lens[t]
 
+    # -- an embedding input: one decode of the whole input in a free sequence, then release
+    def _embed(self, r: EmbedRequest) -> None:
+        with self.lock:
+            self.n_queued -= 1
+        seq = self.free.pop()
+        try:
+            c, n = self.ctx, len(r.tokens)
+            # the sequence starts empty and ends empty; what it held is not there afterwards
+            self._forget(seq)
+            c.seq_rm(seq)
+            t0 = time.perf_counter()
+            c.set_embeddings(True)
+            try:
+                rc = c.decode(r.tokens, pos=list(range(n)), seq=[seq] * n)
+                if rc != 0:
+                    raise RuntimeError(f"llama_decode returned {rc}")
+                if c.pooling == POOLING_NAMES["none"]:
+                    vec = np.stack([c.embeddings_ith(i) for i in range(n)])
+                else:
+                    vec = c.embeddings_seq(seq)
+            finally:
+                c.set_embeddings(False)
+                self.busy_s += time.perf_counter() - t0
+            c.seq_rm(seq)
+            self.embedding_requests += 1
+            self.embedding_tokens += n
+            r.q.put(vec)
+        except Exception as e:  # this input fails; the replica keeps serving
+            r.fail(str(e))
+        finally:
+            self._touch(seq)
+            self.free.append(seq)
+
     # -- admission: prefill into a free sequence, emit the first token
-    def _admit(self, r: Request) -> None:
+    def _admit(self, r) -> None:
+        if isinstance(r, EmbedRequest):
+            return self._embed(r)
         with self.lock:
             self.n_queued -= 1
         cache = self.cache_prompt
@@ -607,8 +683,13 @@ class Engine:
 
     def __init__(self, path: str, n_ctx: int, n_gpu_layers: int, devices: list[int], slots: int = 4,
                  chunk: int = 8, contexts=None, sampling: Optional[SamplingParams] = None, numerics: int = 0,
-                 max_logprobs: int = 0, cache_prompt: bool = False):
+                 max_logprobs: int = 0, cache_prompt: bool = False, embeddings: bool = False,
+                 pooling: Optional[int] = None):
         self.path, self.n_ctx, self.ngl, self.devices = path, n_ctx, n_gpu_layers, devices
+        # /v1/embeddings (--embeddings; off: the routes answer 501) and the pooling type
+        # (--pooling; None: the model's own, known once the contexts exist)
+        self.embeddings = bool(embeddings)
+        self.pooling = pooling
         # the replicas' prompt cache (--cache-prompt); whether it is active is decided per
         # replica when it starts (Replica.cache_prompt), see prompt_cache
         self.cache_prompt = cache_prompt
@@ -651,6 +732,11 @@ class Engine:
                                        bos=m0.bos, eos=m0.eos) if not meta.get("tokenizer.ggml.tokens") \
                     else T.make_tokenizer(meta)
                 self.vocab = TextCodec(tok, meta.get("tokenizer.chat_template"))
+            if self.embeddings:
+                if self.pooling is not None:
+                    for c in ctxs:
+                        c.set_pooling(self.pooling)
+                self.pooling = int(ctxs[0].pooling)
             eog = getattr(self.vocab, "eog", {self.vocab.eos})
             detok = getattr(self.vocab, "detokenize", None)
             self.replicas = [Replica(i, c, self.slots, eog, self.chunk, self.n_ctx,
@@ -674,6 +760,16 @@ class Engine:
             rep = tied[0]
         rep.submit(r)
         return r
+
+    def embed(self, tokens: list[int]) -> np.ndarray:
+        """One embedding input on the least-loaded replica: its pooled vector, not normalised
+        (pooling none: the tokens' rows [n][n_embd])."""
+        r = EmbedRequest(tokens)
+        min(self.replicas, key=lambda x: (x.load(), x.idx)).submit(r)
+        vec = r.q.get()
+        if r.error:
+            raise RuntimeError(r.error)
+        return vec
 
     @property
     def prompt_cache(self) -> bool:
@@ -724,6 +820,8 @@ class Engine:
                          "hbm_gbps": round(r.last_gbps, 1), "busy": round(r.busy_s / up, 3)})
             if r.cache_prompt:
                 reps[-1].update(prompt_tokens=r.prompt_tokens, cached_tokens=r.cached_tokens)
+            if self.embeddings:
+                reps[-1].update(embedding_requests=r.embedding_requests, embedding_tokens=r.embedding_tokens)
         busy = sum(len(r.active) for r in self.replicas)
         return {"slots_idle": self.slots * len(self.replicas) - busy, "slots_processing": busy,
                 "load_s": round(self.load_s, 2), "replicas": reps[:16]}
@@ -832,6 +930,76 @@ class Handler(BaseHTTPRequestHandler):
                 for t, (lp, alt, alp) in zip(ids, entries)]
         return out
 
+    def _embedding_inputs(self, req: dict) -> list[list[int]]:
+        """The request's inputs as token lists; ValueError for what the route does not take."""
+        v = self.engine.vocab
+        inp = req.get("input", req.get("content"))
+        is_ids = lambda x: isinstance(x, list) and bool(x) and all(  # noqa: E731
+            isinstance(t, int) and not isinstance(t, bool) for t in x)
+        if isinstance(inp, str) or is_ids(inp):
+            items = [inp]
+        elif isinstance(inp, list) and inp and all(isinstance(x, str) or is_ids(x) for x in inp):
+            items = inp
+        else:
+            raise ValueError("'input' must be a non-empty string, a list of strings, a list of token ids or a list of those")
+        out = []
+        for x in items:
+            ids = v.tokenize(x, add_bos=True) if isinstance(x, str) else list(x)
+            if not x or not ids:
+                raise ValueError("'input' is empty")
+            if not (0 <= min(ids) and max(ids) < v.n_vocab):
+                raise ValueError("token ids out of range")
+            if len(ids) > self.engine.n_ctx:
+                raise ValueError(f"input is too large to process ({len(ids)} tokens, the context holds "
+                                 f"{self.engine.n_ctx}); increase the context size")
+            out.append(ids)
+        return out
+
+    def _embeddings(self, route: str):
+        eng = self.engine
+        # the reference launches llama-server without embedding support (start.sh passes no
+        # --embeddings; docs/API_REFERENCE.md:537-540 "only available if ... started with
+        # embedding support"): upstream then answers 501 not_supported_error
+        if not getattr(eng, "embeddings", False):
+            return self._send_json(501, _error(
+                501, "This server does not support embeddings. Start it with `--embeddings`", "not_supported_error"))
+        if not eng.ready:
+            return self._send_json(503, _error(503, "Loading model", "unavailable_error"))
+        req = self._body()
+        if req is None or not isinstance(req, dict):
+            return self._send_json(400, _error(400, "invalid JSON body", "invalid_request_error"))
+        none = getattr(eng, "pooling", POOLING_NAMES["mean"]) == POOLING_NAMES["none"]
+        try:
+            if none and route == "/v1/embeddings":
+                raise ValueError("Pooling type 'none' is not OAI compatible. Please use a different pooling type")
+            inputs = self._embedding_inputs(req)
+            norm = req.get("embd_normalize", 2)
+            if isinstance(norm, bool) or norm not in (2, -1):
+                raise ValueError("'embd_normalize' must be 2 (euclidean) or -1 (none)")
+            fmt = req.get("encoding_format", "float")
+            if fmt not in ("float", "base64"):
+                raise ValueError("'encoding_format' must be \"float\" or \"base64\"")
+        except (ValueError, TypeError) as e:
+            return self._send_json(400, _error(400, str(e), "invalid_request_error"))
+
+        def encode(vec: np.ndarray):
+            vec = np.ascontiguousarray(vec, dtype="<f4")
+            if fmt == "base64":
+                return base64.b64encode(vec.tobytes()).decode("ascii")
+            return vec.tolist()
+        data = []
+        try:
+            for i, ids in enumerate(inputs):
+                vec = np.asarray(eng.embed(ids), dtype=np.float32)
+                # pooling none (native routes only): each token's row, as it is (upstream's)
+                emb = [encode(row) for row in vec] if none else encode(normalize(vec, norm))
+                data.append({"object": "embedding", "embedding": emb, "index": i})
+        except Exception as e:  # a failed llama_decode: OpenAI-shaped 500, not a dropped socket
+            return self._send_json(500, _error(500, str(e), "server_error"))
+        n = sum(len(ids) for ids in inputs)
+        return self._send_json(200, {"object": "list", "data": data, "model": req.get("model") or eng.model_id,
+                                     "usage": {"prompt_tokens": n, "total_tokens": n}})
+
     # ---- routes
     def do_GET(self):
         eng = self.engine
@@ -858,11 +1026,7 @@ class Handler(BaseHTTPRequestHandler):
         if not self._authorized(route):
             return self._send_json(401, _error(401, "Invalid API Key", "authentication_error"))
         if route in ("/v1/embeddings", "/embeddings", "/embedding"):
-            # the reference launches llama-server without embedding support (start.sh
-            # passes no --embeddings; docs/API_REFERENCE.md:537-540 "only available if ...
-            # started with embedding support"): upstream then answers 501 not_supported_error
-            return self._send_json(501, _error(
-                501, "This server does not support embeddings. Start it with `--embeddings`", "not_supported_error"))
+            return self._embeddings(route)
         if route not in ("/v1/completions", "/v1/chat/completions", "/completion"):
             return self._send_json(404, _error(404, "File Not Found", "not_found_error"))
         if not eng.ready:
@@ -1063,6 +1227,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-cache-prompt", dest="cache_prompt", action="store_false",
                     help="prefill every prompt in full (the default; also LLMI_CACHE_PROMPT=0, or "
                          "cache_prompt: false in a request)")
+    ap.add_argument("--embeddings", "--embedding", dest="embeddings", action="store_true",
+                    default=os.environ.get("LLMI_EMBEDDINGS", "0") == "1",
+                    help="serve /v1/embeddings (also LLMI_EMBEDDINGS=1); without it the route answers 501")
+    ap.add_argument("--pooling", choices=sorted(POOLING_NAMES), default=None,
+                    help="pooling of the embeddings (default: the model's GGUF pooling_type, else none)")
     ap.add_argument("--numerics", choices=NUMERICS_CHOICES, default=None,
                     help="fp32 association of every kernel: ggml's generic order, or the oracle's model of "
                          "upstream's x86 AVX2 association (non-repack); '-fa': decode attention in ggml's CPU "
@@ -1114,7 +1283,8 @@ def main(argv=None) -> int:
                         presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty, seed=args.seed)
     eng = Engine(args.model, args.ctx_size, args.ngl, list(range(max(1, args.replicas))), slots=args.parallel,
                  chunk=args.decode_chunk, sampling=sp, numerics=numerics_value(args.numerics),
-                 max_logprobs=args.max_logprobs, cache_prompt=args.cache_prompt)
+                 max_logprobs=args.max_logprobs, cache_prompt=args.cache_prompt, embeddings=args.embeddings,
+                 pooling=POOLING_NAMES[args.pooling] if args.pooling else None)
     srv = make_server(eng, args.host, args.port, key)
     threading.Thread(target=eng.load, daemon=True).start()
     print(f"[llmi-server] listening on {args.host}:{args.port}", file=sys.stderr, flush=True)
