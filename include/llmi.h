@@ -380,7 +380,7 @@ struct llama_model* llmi_model_load_fanout(const char* path, struct llama_model_
                                            int32_t nranks, int32_t rank);
 struct llama_model* llmi_model_load_replicated(const char* path, struct llama_model_params params,
                                                const int32_t* devices, int32_t n, struct llama_model** out);
-/* The fan-out schedule (engine.cpp fanout_plan; host only, for tests): pieces of `chunk`
+/* The fan-out schedule (model.cpp fanout_plan; host only, for tests): pieces of `chunk`
  * bytes over an arena of arena_bytes; ready[k] = the index of the first upload prefix
  * (prefix_ends, ascending) that covers piece k.  Returns the number of pieces. */
 int32_t llmi_fanout_plan(uint64_t arena_bytes, uint64_t chunk, const uint64_t* prefix_ends, int32_t n_prefix,
@@ -421,7 +421,7 @@ int32_t llmi_repack(int32_t type, const void* raw_dev, void* w_dev, int64_t rows
 /* y = W . quantize(norm_w ? rmsnorm(x)*norm_w : x); mode 0 store, 1 accumulate (y += .) */
 int32_t llmi_matvec(int32_t type, const void* w_dev, int64_t rows, int64_t cols, const float* x_dev,
                     const float* norm_w_dev, float eps, float* y_dev, int32_t mode);
-/* batched prefill GEMM (prefill.hip.inc): Y[t] = W . quantize(norm_w ? rmsnorm(x[t])*norm_w
+/* batched prefill GEMM (prefill.hip): Y[t] = W . quantize(norm_w ? rmsnorm(x[t])*norm_w
  * : x[t]) for n_tok rows x[t] of `cols` floats (row-major), Y [n_tok][rows]; must equal
  * n_tok llmi_matvec calls bit for bit.  usec (optional): device time of the GEMM launch. */
 int32_t llmi_pf_gemm(int32_t type, const void* w_dev, int64_t rows, int64_t cols, const float* x_dev,

@@ -504,7 +504,7 @@ hipError_t launch_pf_attn_x86(const PfAttn& a, int n_head, int n_head_kv, int he
     const int g = n_head / n_head_kv;
     if (a.max_kv > pf_attn_x86_max_kv(n_head, n_head_kv, head_dim)) return hipErrorInvalidValue;
     // (gfx950 takes up to 160 KiB of dynamic LDS as is; the attribute call is refused,
-    // prefill.hip.inc launch_pf_attn)
+    // prefill.hip launch_pf_attn)
     const size_t lds = (size_t)g * ((a.max_kv + 31) & ~31) * 4;
 #define LLMI_PA86(D_, G_)                                                                     \
     if (head_dim == D_ && g == G_) {                                                          \

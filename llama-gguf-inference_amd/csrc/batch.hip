@@ -389,7 +389,7 @@ __device__ __forceinline__ void bm_terms(const BmStage<T, NW>& st, float (&tm)[N
             for (int i = 0; i < 4; ++i) tm[wi][8][i] = sm[i];
         } else if constexpr (!X86) {
             // sumi = mins . bsum pairs on the MFMA (every product and partial sum an integer
-            // < 2^24: exact, prefill.hip.inc k_pf_quant); the term -(dmin * d_a) * sumi
+            // < 2^24: exact, prefill.hip k_pf_quant); the term -(dmin * d_a) * sumi
             f4 sm{0.f, 0.f, 0.f, 0.f};
             if constexpr (T != T_Q6_K) sm = mfma16(st.bs, bm, f4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
@@ -981,7 +981,7 @@ static hipError_t bmm_launch(const MVArgs& a, const void* aq, const void* abf, c
     auto k = dma ? k_bmd<T, EPI, X86> : k_bmm<T, EPI>;
     const size_t lds = dma ? bmd_lds<T, NW, X86>() : (size_t)(2 * kBmW + 1) * NW * 9 * 32 * 16;
     // shape / occupancy rejections are hipErrorNotSupported: the caller then runs the two
-    // type groups as separate launches (engine.cpp) instead of failing the step
+    // type groups as separate launches (decode_step.cpp) instead of failing the step
     if (lds > 160 * 1024) return hipErrorNotSupported;
     const int cap = bmm_cap((const void*)k, lds);
     int rows = 0;
@@ -1006,7 +1006,7 @@ static hipError_t bmm2_launch(const MVArgs& a1, const MVArgs& a2, const void* aq
     auto k = k_bmd2<T, T2, X86>;
     const size_t lds = std::max(bmd_lds<T, 1, X86>(), bmd_lds<T2, 1, X86>());
     // shape / occupancy rejections are hipErrorNotSupported: the caller then runs the two
-    // type groups as separate launches (engine.cpp) instead of failing the step
+    // type groups as separate launches (decode_step.cpp) instead of failing the step
     if (lds > 160 * 1024) return hipErrorNotSupported;
     const int cap = bmm_cap((const void*)k, lds);
     int r1 = 0, r2 = 0;

@@ -18,21 +18,12 @@ using namespace llmi;
 
 namespace {
 bool ensure_outs(llama_context* ctx, int n) {
-    const int V = ctx->c.m->hp.n_vocab;
-    if (n <= ctx->outs_cap) return true;
-    if (ctx->outs) (void)hipFree(ctx->outs);
-    ctx->outs = nullptr;
-    ctx->outs_cap = 0;
-    if (hipMalloc(&ctx->outs, (size_t)n * V * 4) != hipSuccess) { set_err("hipMalloc logits outputs"); return false; }
-    ctx->outs_cap = n;
-    if (n > ctx->keys_cap) {
-        if (ctx->keys_pinned) (void)hipHostFree(ctx->keys_pinned);
-        ctx->keys_pinned = nullptr;
-        if (hipHostMalloc((void**)&ctx->keys_pinned, (size_t)n * 8 * kArgSlots, hipHostMallocDefault) != hipSuccess) {
-            set_err("hipHostMalloc");
-            return false;
-        }
-        ctx->keys_cap = n;
+    DevPool& pool = ctx->c.pool;  // the context's: freed with it, inside its device scope
+    const size_t V = (size_t)ctx->c.m->hp.n_vocab;
+    if (pool.grow({{&ctx->outs, V * 4}}, ctx->outs_cap, n, n) != hipSuccess) { set_err("hipMalloc logits outputs"); return false; }
+    if (pool.grow({{&ctx->keys_pinned, 8 * kArgSlots, true}}, ctx->keys_cap, n, n) != hipSuccess) {
+        set_err("hipHostMalloc");
+        return false;
     }
     return true;
 }
@@ -54,6 +45,22 @@ void logprob_readback_seq(Context& c, const LogprobOut& lp, int k, int n_gen) {
     if (lp.n_top[k] < 0) return;  // its entries stay as the caller left them
     const size_t at = (size_t)k * n_gen;
     logprob_readback(c, k, n_gen, lp.tok_lp + at, lp.top_id + at * kLogprobMaxTop, lp.top_lp + at * kLogprobMaxTop);
+}
+
+// the end of a generate call, its read-backs enqueued: the sync, the fault check and the
+// call's time and bytes; 0, or the call's error code with the error set
+int32_t generate_finish(Context& c, const std::string& who, double bytes) {
+    context_fault_readback(c);
+    hipError_t e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) { set_err(who + hip_err(e)); return -4; }
+    std::string err;
+    if (!context_fault_ok(c, err)) { set_err(who + err); return -6; }
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, c.ev0, c.ev1);
+    c.last_us = ms * 1e3;
+    c.last_bytes = bytes;
+    c.n_outputs = 0;
+    return 0;
 }
 
 // llmi_generate_greedy's body; sampled: the steps end with k_sample (the caller has uploaded
@@ -88,18 +95,10 @@ int32_t generate_one(const char* name, llama_context* ctx, llama_token first, in
         (void)hipMemcpyAsync(h.data(), c.hist + pos0 + 1, (size_t)(n_gen - 1) * 4, hipMemcpyDeviceToHost, c.stream);
     (void)hipMemcpyAsync(keys, &c.st->key[(pos0 + n_gen - 1) & 1][0], sizeof(keys), hipMemcpyDeviceToHost, c.stream);
     if (lp) logprob_readback_seq(c, *lp, 0, n_gen);
-    context_fault_readback(c);
-    hipError_t e = hipStreamSynchronize(c.stream);
-    if (e != hipSuccess) { set_err(who + hip_err(e)); return -4; }
-    if (!context_fault_ok(c, err)) { set_err(who + err); return -6; }
+    if (const int32_t rc = generate_finish(c, who, bytes)) return rc;
     for (int k = 0; k + 1 < n_gen; ++k) out[k] = h[(size_t)k];
     out[n_gen - 1] = (llama_token)key_token(keys);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, c.ev0, c.ev1);
-    c.last_us = ms * 1e3;
-    c.last_bytes = bytes;
     c.n_past = pos0 + n_gen;
-    c.n_outputs = 0;
     return n_gen;
 }
 
@@ -170,20 +169,12 @@ int32_t generate_batch(const char* name, llama_context* ctx, int32_t n, const in
                              8 * kArgSlots, hipMemcpyDeviceToHost, c.stream);
         if (lp) logprob_readback_seq(c, *lp, k, n_gen);
     }
-    context_fault_readback(c);
-    hipError_t e = hipStreamSynchronize(c.stream);
-    if (e != hipSuccess) { set_err(who + hip_err(e)); return -4; }
-    if (!context_fault_ok(c, err)) { set_err(who + err); return -6; }
+    if (const int32_t rc = generate_finish(c, who, bytes)) return rc;
     for (int k = 0; k < n; ++k) {
         for (int j = 0; j + 1 < n_gen; ++j) out[(size_t)k * n_gen + j] = h[(size_t)k * n_gen + j];
         out[(size_t)k * n_gen + n_gen - 1] = (llama_token)key_token(keys.data() + (size_t)k * kArgSlots);
         set_seq_past(c, seqs[k], pos0[k] + n_gen);
     }
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, c.ev0, c.ev1);
-    c.last_us = ms * 1e3;
-    c.last_bytes = bytes;
-    c.n_outputs = 0;
     return n_gen;
 }
 }  // namespace
@@ -270,9 +261,7 @@ struct llama_context* llama_init_from_model(struct llama_model* model, struct ll
 void llama_free(struct llama_context* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->c.device);  // never reads the model: it may be freed already
-    if (ctx->outs) (void)hipFree(ctx->outs);
-    if (ctx->keys_pinned) (void)hipHostFree(ctx->keys_pinned);
-    delete ctx;
+    delete ctx;  // outs and keys_pinned are the context pool's
 }
 
 struct llama_batch llama_batch_get_one(llama_token* tokens, int32_t n_tokens) {

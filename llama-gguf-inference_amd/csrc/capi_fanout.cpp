@@ -26,11 +26,11 @@ int32_t llmi_model_arena(const struct llama_model* model, void** dev_ptr, uint64
 // synchronous hash of device memory on `device` (launch_arena_hash, kernels.hip)
 static bool device_hash(int device, const void* p, size_t bytes, uint64_t* out, std::string& err) {
     if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice"; return false; }
+    DevPool P;
     unsigned long long* d = nullptr;
-    if (hipMalloc(&d, 8) != hipSuccess) { err = "hipMalloc (hash)"; return false; }
+    if (P.alloc(d, 8) != hipSuccess) { err = "hipMalloc (hash)"; return false; }
     hipError_t e = launch_arena_hash(p, bytes, d, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, d, 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) { err = std::string("arena hash: ") + hipGetErrorString(e); return false; }
     return true;
 }
@@ -62,7 +62,7 @@ int32_t llmi_device_hash(const void* dev_ptr, uint64_t bytes, uint64_t* out) {
 // still uploading (llmi_model_load_fanout / llmi_model_load_replicated), piece k is issued
 // as soon as the upload stream has completed the arena prefix that covers it (an event on
 // the upload stream, waited on by the broadcast streams), so the xGMI broadcast runs
-// behind the host-to-device copy instead of after it.  engine.cpp fanout_plan states the
+// behind the host-to-device copy instead of after it.  model.cpp fanout_plan states the
 // schedule; tests/test_fanout_plan.py checks it.
 namespace {
 struct Fanout {
@@ -153,10 +153,11 @@ struct Fanout {
             if (!device_hash(dev[r], buf[r], bytes, &own[r], e)) { hashed = false; err = e; }
         }
         std::vector<unsigned long long*> w(n, nullptr);
+        std::vector<DevPool> pools(n);  // one per rank: freed below with the rank's device current
         bool alloc = true;
         for (size_t r = 0; r < n; ++r) {
             (void)hipSetDevice(dev[r]);
-            if (hipMalloc(&w[r], 16) != hipSuccess) alloc = false;
+            if (pools[r].alloc(w[r], 16) != hipSuccess) alloc = false;
         }
         // the root's words: status (0 ok), its arena hash; other ranks' buffers are overwritten
         const bool is_root = rank0;
@@ -197,7 +198,7 @@ struct Fanout {
         }
         for (size_t r = 0; r < n; ++r) {
             (void)hipSetDevice(dev[r]);
-            if (w[r]) (void)hipFree(w[r]);
+            pools[r].free_all();
         }
         (void)hipSetDevice(dev[0]);
         return ok_all;

@@ -14,24 +14,7 @@
 using namespace llmi;
 
 namespace {
-// the device allocations of one hook call, freed on every way out; after a failure every
-// further request returns null and `err` keeps the first error
-struct DevPool {
-    std::vector<void*> all;
-    hipError_t err = hipSuccess;
-    template <class T>
-    T* get(size_t bytes, bool zero = true) {
-        void* p = nullptr;
-        if (err == hipSuccess) err = hipMalloc(&p, bytes ? bytes : 1);
-        if (err != hipSuccess) return nullptr;
-        all.push_back(p);
-        if (zero) err = hipMemset(p, 0, bytes);
-        return (T*)p;
-    }
-    ~DevPool() {
-        for (void* p : all) (void)hipFree(p);
-    }
-};
+// (the device allocations of one hook call: a local DevPool's get(), dev_mem.h)
 // launch_pf_quant's outputs for tpad token rows (llmi_pf_gemm's sizes), zeroed: the padded
 // rows are read
 struct QuantScratch {
@@ -185,7 +168,7 @@ int32_t llmi_engine_trace(struct llama_context* ctx, llama_token first, int32_t 
     const int kv_bound = kv_bucket_bound(pos0 + 1, c.n_ctx);
     std::string err;
     int rc = 0;
-    if (!c.le_trace && hipMalloc(&c.le_trace, n * 8) != hipSuccess) { set_err("llmi_engine_trace: hipMalloc"); return -3; }
+    if (!c.le_trace && c.pool.alloc(c.le_trace, n * 8) != hipSuccess) { set_err("llmi_engine_trace: hipMalloc"); return -3; }
     (void)hipMemsetAsync(c.le_trace, 0, n * 8, c.stream);
     bool ok = launch_state_set(c.st, first, pos0, c.stream) == hipSuccess && step_enqueue(c, kv_bound, err);
     c.le_trace_layer = layer;

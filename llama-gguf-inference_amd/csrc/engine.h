@@ -11,6 +11,7 @@
 #include <functional>
 
 #include "common.h"
+#include "dev_mem.h"
 #include "gguf.h"
 #include "kernels.h"
 #include "tokenizer.h"
@@ -85,6 +86,42 @@ struct Prof {
     ~Prof();
 };
 
+// Captures what `enqueue` puts on `s` (thread-local capture mode) into an executable
+// graph.  Null and err set when capture, enqueue ("capture: " + its error) or
+// instantiation fails; the captured graph itself is destroyed on every way out.
+hipGraphExec_t capture_graph(hipStream_t s, const std::function<bool(std::string&)>& enqueue, std::string& err);
+
+// How a decode step ends.  STEP_SAMPLED: with k_sample over its logits rows (sample.hip);
+// STEP_LOGPROBS: with k_logprob before it and k_logprob_pick after it (logprob.hip).
+enum : int { STEP_GREEDY = 0, STEP_SAMPLED = 1, STEP_LOGPROBS = 2, STEP_NTAILS = 3 };
+
+// A context's step graphs, cached apart per tail: the single-sequence steps by KV bucket *
+// 256 + sequence, the batched steps by "bucket:slots,sequence,...".
+struct GraphCache {
+    std::map<int, hipGraphExec_t> one[STEP_NTAILS];
+    std::map<std::string, hipGraphExec_t> batch[STEP_NTAILS];
+    std::vector<hipGraphExec_t> all;  // every graph of the maps, for destroy()
+    std::map<int, hipGraphExec_t>& by(int tail, int) { return one[tail]; }
+    std::map<std::string, hipGraphExec_t>& by(int tail, const std::string&) { return batch[tail]; }
+    // the graph of (tail, key), captured on `s` from `enqueue` when the key is new (null, err set: failed)
+    template <class Key, class F>
+    hipGraphExec_t find_or_capture(int tail, const Key& key, hipStream_t s, F&& enqueue, std::string& err) {
+        auto& graphs = by(tail, key);
+        auto it = graphs.find(key);
+        if (it == graphs.end()) {
+            hipGraphExec_t ex = capture_graph(s, enqueue, err);
+            if (!ex) return nullptr;
+            all.push_back(ex);
+            it = graphs.emplace(key, ex).first;
+        }
+        return it->second;
+    }
+    void destroy() {  // with the context's device current
+        for (hipGraphExec_t g : all) (void)hipGraphExecDestroy(g);
+        all.clear();
+    }
+};
+
 struct Context {
     Model* m = nullptr;
     int device = 0;                         // m->device, kept so teardown never reads *m
@@ -102,6 +139,9 @@ struct Context {
     bool use_graphs = true;
     hipStream_t stream = nullptr;
     int max_blocks = 1024;
+    // Every device and pinned block below is allocated through `pool`, which frees them at
+    // teardown (~Context); none is zeroed by it (the memsets run on `stream`).
+    DevPool pool;
     // device
     float *x = nullptr, *q = nullptr, *att = nullptr, *h = nullptr, *logits = nullptr, *scores = nullptr;
     float* rope = nullptr;
@@ -114,7 +154,7 @@ struct Context {
     std::vector<unsigned long long> out_keys;  // per output: argmax key
     int n_outputs = 0;
     int n_past = 0;
-    std::map<int, hipGraphExec_t> graphs;   // by KV bucket * 256 + sequence
+    GraphCache graphs;
     // batched decode (batch.hip): kMaxBatch rows each, allocated on first use
     float *bx = nullptr, *bq = nullptr, *batt = nullptr, *bh = nullptr, *blogits = nullptr, *bscores = nullptr;
     int *btpos = nullptr, *btseq = nullptr;
@@ -123,7 +163,6 @@ struct Context {
     float* bad = nullptr;
     void* babf = nullptr;          // k_bmm: the step's bsum pairs as sumi MFMA fragments (pf_abf_off)
     std::vector<int> btseq_host;            // the slot -> sequence map btseq holds
-    std::map<std::string, hipGraphExec_t> bgraphs;  // by (slots, sequences, KV bucket)
     // device sampling (sample.hip): the slots' sampler records and this call's uniforms, filled
     // by sample_prepare before the steps; the sampled step graphs (a greedy step + k_sample)
     // are cached apart from the greedy ones
@@ -132,8 +171,6 @@ struct Context {
     int suni_cap = 0;
     std::vector<SampleRec> srec_host;       // what the pending copies read, alive until the call's sync
     std::vector<double> suni_host;
-    std::map<int, hipGraphExec_t> sgraphs;
-    std::map<std::string, hipGraphExec_t> sbgraphs;
     // device log-probabilities (logprob.hip): the slots' records and the output rings they
     // point into, filled by logprob_prepare; the steps with logprobs (logits, k_logprob,
     // k_sample, k_logprob_pick) have graphs of their own
@@ -144,8 +181,6 @@ struct Context {
     float* lp_win_raw = nullptr;
     int lp_cap = 0;
     std::vector<LogprobRec> lrec_host;
-    std::map<int, hipGraphExec_t> lgraphs;
-    std::map<std::string, hipGraphExec_t> lbgraphs;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     unsigned* fault_dev = nullptr;          // device fault word: a bounded in-kernel wait gave up
     unsigned* fault_host = nullptr;         // pinned copy, read back with every decode call
@@ -182,6 +217,8 @@ struct Context {
 };
 
 // all return false and set err on failure
+
+// ---- model.cpp: GGUF model -> device weight arena ----
 // Upload progress hook (replica fan-out pipelined behind the H2D): called
 // after each tensor's chunks are enqueued on the upload stream `us` with the end of the
 // arena prefix that is complete once `us` reaches that point (tensors are planned in
@@ -191,29 +228,34 @@ bool model_load(const std::string& path, int device, bool vocab_only, bool no_up
                 const UploadHook* hook = nullptr, int numerics = NUMERICS_GENERIC);
 // the upload half of model_load (after a load with no_upload)
 bool model_upload(Model& m, std::string& err, const UploadHook* hook = nullptr);
+// arena layout of a model for another device (replica); no upload
+bool model_clone_layout(const Model& src, int device, Model& dst, std::string& err);
 // a matrix of the arena as a matvec segment (rows start at row0 of the launch)
 Seg seg_of(const Model& m, const DevMat& d, int row0);
-
+size_t model_tensor_bytes(const Model& m);
+double bytes_per_token(const Model& m, int n_kv);
 // Fan-out pieces of an arena: [k * chunk, min((k + 1) * chunk, arena_bytes)).  Piece k is
 // issued after the first upload event whose prefix covers its end; ready[k] = index of
 // that event in prefix_ends (ascending).  Returns the number of pieces.
 size_t fanout_plan(size_t arena_bytes, size_t chunk, const std::vector<size_t>& prefix_ends, std::vector<int>& ready);
 constexpr size_t kFanoutChunk = 256u << 20;  // 256 MB broadcasts behind the upload
+
+// ---- context.cpp: the context, its sampler / logprob records and its embeddings ----
+std::string hip_err(hipError_t e);
+// matvec grid cap = CUs x wg_per_cu() workgroups (env LLMI_WG_PER_CU, read when a context
+// is created; default 2: measured best on every config, profiles/r01/wg_sweep.md)
+int wg_per_cu();
+int mv_grid_cap(int device);  // at least 64; 0: the device query failed
 bool context_init(Model* m, int n_ctx, bool use_graphs, int n_seq, Context& c, std::string& err);
 // point the single-sequence paths (step_run, prefill_enqueue, state) at sequence s
 void context_select_seq(Context& c, int s);
+void context_clear(Context& c);
 // clear one sequence's KV cache, history and state
 void context_clear_seq(Context& c, int s);
-// one batched decode step of nt sequences seqs[0..nt) (their StepStates hold token and
-// position), replayed from a graph per (slots, sequences, KV bucket of max_pos)
-// (tail STEP_SAMPLED: the step ends with k_sample over its logits rows, sample.hip;
-// STEP_LOGPROBS: with k_logprob before it and k_logprob_pick after it, logprob.hip)
-enum : int { STEP_GREEDY = 0, STEP_SAMPLED = 1, STEP_LOGPROBS = 2 };
-bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, int tail = STEP_GREEDY);
-// enqueue one decode step for a state already set (token_in/pos_next); kv_bound >= pos+1
-bool step_enqueue(Context& c, int kv_bound, std::string& err, int tail = STEP_GREEDY);
-// run one step via the cached graph of its KV bucket (or eagerly)
-bool step_run(Context& c, int pos, std::string& err, int tail = STEP_GREEDY);
+// enqueue the device fault word's read-back (before the call's stream sync) ...
+void context_fault_readback(Context& c);
+// ... and after the sync: false (err set, word re-armed) if an in-kernel wait gave up
+bool context_fault_ok(Context& c, std::string& err);
 // uploads slot k's record recs[k] (k < n; the other slots greedy) and its n_gen uniforms
 // uniforms[k * n_gen ..], drawn by the steps at positions pos0[k] .., on c.stream
 bool sample_prepare(Context& c, int n, const SampleRec* recs, const int* pos0, const double* uniforms, int n_gen,
@@ -223,17 +265,6 @@ bool sample_prepare(Context& c, int n, const SampleRec* recs, const int* pos0, c
 bool logprob_prepare(Context& c, int n, const int32_t* n_top, const int* pos0, int n_gen, std::string& err);
 // enqueue the copies of slot k's n_gen ring entries to the host arrays (before the call's sync)
 void logprob_readback(Context& c, int k, int n_gen, double* tok_lp, int32_t* top_id, double* top_lp);
-double bytes_per_token(const Model& m, int n_kv);
-// batched prefill: can the model's layers run through the MFMA prefill path?  (flash-
-// attention numerics: only with LLMI_FA_PREFILL=1, read on every call)
-bool prefill_supported(const Model& m);
-// positions the batched prefill's attention reaches: the context when the tiled kernel
-// (k_pf_fa) takes the model's heads, else the LDS kernels' pf_max_kv()
-int prefill_max_kv(Context& c);
-// run tokens [0, n) at positions pos0.. through every layer as batched launches (KV
-// cache written, no logits); enqueued on c.stream, no synchronisation
-bool prefill_enqueue(Context& c, const int32_t* tokens, int n, int pos0, std::string& err);
-void context_clear(Context& c);
 // embeddings: room for `rows` result rows in c.embd_out (and the mean's scratch), allocated on first use
 constexpr int kEmbdMaxChunk = 4096;  // tokens per embd_pool_enqueue call (the largest prefill ubatch)
 bool embd_alloc(Context& c, int rows, std::string& err);
@@ -241,22 +272,25 @@ bool embd_alloc(Context& c, int rows, std::string& err);
 // sequence embd_begin announced; enqueued on c.stream after the launches that wrote x
 void embd_begin(Context& c, int n_total, float* dst);
 bool embd_pool_enqueue(Context& c, const float* x, int64_t ldx, int n_tok, std::string& err);
-// enqueue the device fault word's read-back (before the call's stream sync) ...
-void context_fault_readback(Context& c);
-// ... and after the sync: false (err set, word re-armed) if an in-kernel wait gave up
-bool context_fault_ok(Context& c, std::string& err);
-size_t model_tensor_bytes(const Model& m);
-// arena layout of a model for another device (replica); no upload
-bool model_clone_layout(const Model& src, int device, Model& dst, std::string& err);
 
-std::string hip_err(hipError_t e);
-// matvec grid cap = CUs x wg_per_cu() workgroups (env LLMI_WG_PER_CU, read when a context
-// is created; default 2: measured best on every config, profiles/r01/wg_sweep.md)
-int wg_per_cu();
-int mv_grid_cap(int device);  // at least 64; 0: the device query failed
-// Captures what `enqueue` puts on `s` (thread-local capture mode) into an executable
-// graph.  Null and err set when capture, enqueue ("capture: " + its error) or
-// instantiation fails; the captured graph itself is destroyed on every way out.
-hipGraphExec_t capture_graph(hipStream_t s, const std::function<bool(std::string&)>& enqueue, std::string& err);
+// ---- decode_step.cpp: the single-sequence and the batched decode step ----
+// enqueue one decode step for a state already set (token_in/pos_next); kv_bound >= pos+1
+bool step_enqueue(Context& c, int kv_bound, std::string& err, int tail = STEP_GREEDY);
+// run one step via the cached graph of its KV bucket (or eagerly)
+bool step_run(Context& c, int pos, std::string& err, int tail = STEP_GREEDY);
+// one batched decode step of nt sequences seqs[0..nt) (their StepStates hold token and
+// position), replayed from a graph per (slots, sequences, KV bucket of max_pos)
+bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, int tail = STEP_GREEDY);
+
+// ---- prefill_step.cpp: the batched prefill ----
+// can the model's layers run through the MFMA prefill path?  (flash-attention numerics:
+// only with LLMI_FA_PREFILL=1, read on every call)
+bool prefill_supported(const Model& m);
+// positions the batched prefill's attention reaches: the context when the tiled kernel
+// (k_pf_fa) takes the model's heads, else the LDS kernels' pf_max_kv()
+int prefill_max_kv(Context& c);
+// run tokens [0, n) at positions pos0.. through every layer as batched launches (KV
+// cache written, no logits); enqueued on c.stream, no synchronisation
+bool prefill_enqueue(Context& c, const int32_t* tokens, int n, int pos0, std::string& err);
 
 }  // namespace llmi

@@ -192,16 +192,16 @@ struct EmbArgs {
     int n_ctx = 0;
 };
 
-// Batched prefill (prefill.hip.inc): one launch per linear layer over T prompt tokens.
+// Batched prefill (prefill.hip): one launch per linear layer over T prompt tokens.
 struct PfGemm {
     Seg w, w2;                 // weights (SWIGLU: w = gate, w2 = up)
     int rows = 0, cols = 0;
     int T = 0;                 // tokens (activation rows are padded to a multiple of 64)
     int xcd_map = 0;           // set by the launcher: XCD-aware tile order, token-group chunk (k_pf_gemm; 0 off)
-    const void* aq = nullptr;     // f16 MFMA fragments of the q8 activations (prefill.hip.inc pf_aq_off), Tpad x cols x 2 B
+    const void* aq = nullptr;     // f16 MFMA fragments of the q8 activations (prefill.hip pf_aq_off), Tpad x cols x 2 B
     const int16_t* abs = nullptr; // [Tpad][cols/32] bsum pairs (q8_K)
     const float* ad = nullptr;    // [Tpad][cols/256] (q8_K) or [Tpad][cols/32] (q8_0) d
-    const void* abf = nullptr;    // K-quants: the bsum pairs as sumi MFMA fragments (prefill.hip.inc pf_abf_off)
+    const void* abf = nullptr;    // K-quants: the bsum pairs as sumi MFMA fragments (prefill.hip pf_abf_off)
     float* y = nullptr;        // STORE / ADD / SWIGLU / QKV q: [T][ldy]
     int ldy = 0;
     int part = 0;              // QKV: 0 q (RoPE, f32 to y), 1 k (RoPE, f16 cache), 2 v (f16 cache)

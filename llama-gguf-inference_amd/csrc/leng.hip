@@ -35,7 +35,7 @@
 // sc1 loads, s_sleep), then sets an LDS word for the others; every load of a handed-off
 // vector is an sc1 load.  This is MI355X_MICROARCH.md §visibility's "Valid forms" row 1
 // (sc1 stores / counter / sc1 loads, one workgroup per CU) — no acquire fence.  The
-// counters are zeroed by a memset node at the start of every step (engine.cpp).
+// counters are zeroed by a memset node at the start of every step (decode_step.cpp).
 // Every spin is bounded: a timed-out wait ORs a code into the context's fault word, sets
 // ctl.dead and every wave of the workgroup leaves (the host reports the step as failed).
 #include "kernels.h"

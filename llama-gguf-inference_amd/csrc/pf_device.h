@@ -1,6 +1,6 @@
-// pf_device.h — the f16-MFMA building blocks of the K-quant GEMMs (prefill.hip.inc
+// pf_device.h — the f16-MFMA building blocks of the K-quant GEMMs (prefill.hip
 // k_pf_gemm, batch.hip k_bmm): the activation fragment layout, one lane's weights of a
-// 256-element stage, and the exact B fragments q * scale (prefill.hip.inc header: why
+// 256-element stage, and the exact B fragments q * scale (prefill.hip header: why
 // every integer sum is exact on the f16 MFMA).
 #pragma once
 #include "mv_device.h"

@@ -52,7 +52,7 @@ def device_count() -> int:
 
 
 def fanout_plan(arena_bytes: int, chunk: int, prefix_ends: Sequence[int]) -> list[int]:
-    """The replica fan-out schedule (engine.cpp fanout_plan): for each chunk-sized piece of
+    """The replica fan-out schedule (model.cpp fanout_plan): for each chunk-sized piece of
     the arena, the index of the first upload prefix that covers it.  Host only."""
     n = len(prefix_ends)
     pe = (C.c_uint64 * max(1, n))(*prefix_ends)

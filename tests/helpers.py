@@ -31,7 +31,7 @@ def random_blocks(qtype: int, rows: int, cols: int, rng: np.random.Generator) ->
 
 
 # ---- edge inputs: blocks and activations at the bounds of the kernels' exactness argument ----
-# (prefill.hip.inc header, mv_device.h unit_terms).  Every builder returns (raw, acts): raw
+# (prefill.hip header, mv_device.h unit_terms).  Every builder returns (raw, acts): raw
 # ggml blocks and the activation families that go with them, acts = [(name, make)], where
 # make(rng) draws one f32[cols] vector of the family.
 SAT_VARIANTS = {Q4_K: (0,), Q5_K: (0,), Q6_K: (0, 1), Q8_0: (0, 1)}

@@ -80,7 +80,7 @@ def expf_np(x: np.ndarray, subnormal_branch: bool = True) -> np.ndarray:
 
 
 def pf_expf_np(x: np.ndarray) -> np.ndarray:
-    """csrc/prefill.hip.inc pf_expf: llmi_expf's polynomial, the 2^n scaling as ONE correctly
+    """csrc/prefill.hip pf_expf: llmi_expf's polynomial, the 2^n scaling as ONE correctly
     rounded ldexp (exact in double, one rounding to float32, subnormals included)."""
     x = np.asarray(x, F32)
     with np.errstate(over="ignore", invalid="ignore", under="ignore"):

@@ -1,4 +1,4 @@
-"""The replica fan-out schedule (engine.cpp fanout_plan), host only:
+"""The replica fan-out schedule (model.cpp fanout_plan), host only:
 the arena goes out in 256 MB pieces, each issued after the first upload prefix that
 covers it -- so the broadcast of piece k overlaps the upload of what follows it.
 (llmi_model_load_fanout / llmi_model_load_replicated run this schedule on RCCL;

@@ -2,7 +2,7 @@
 
 Every quantized linear kernel claims bit-equality with ggml's generic order (and with the
 x86 order in x86 numerics) on the strength of magnitude bounds stated in comments
-(prefill.hip.inc header, batch.hip, mv_device.h unit_terms).  These tests feed the inputs
+(prefill.hip header, batch.hip, mv_device.h unit_terms).  These tests feed the inputs
 that sit ON those bounds (tests/helpers.py; checked on the CPU by
 tests/test_matvec_edge_inputs.py) through every such kernel:
 
@@ -178,7 +178,7 @@ def test_matvec_edges_accumulate(gpu, qtype, num):
 
 
 # ---- llmi_pf_gemm (k_pf_gemm) --------------------------------------------------------------
-# The launcher (prefill.hip.inc pf_gemm_launch) takes the 64-token-workgroup kernel
+# The launcher (prefill.hip pf_gemm_launch) takes the 64-token-workgroup kernel
 # k_pf_gemm<.., NG = 2> only in generic numerics, with the pf_gemm_ng option at 2, above 32
 # tokens, and when ceil(rows / 64) * ceil(T / 64) workgroups fill every CU; else the 32-token
 # kernel (NG = 1), which x86 numerics always takes.  At PF_SHAPES the grid never fills the

@@ -142,7 +142,7 @@ def test_pf_attention_rejects_bad_shapes(gpu):
 @pytest.mark.parametrize("H,HK,D,T,pos0", [(32, 8, 128, 37, 700), (32, 4, 64, 40, 300), (8, 8, 64, 70, 130)])
 def test_pf_attention_kernel_configurations(gpu, cfg, H, HK, D, T, pos0):
     """k_pf_fa's other configurations (row blocks per workgroup, waves per block, e kept
-    from pass 2 or taken again; prefill.hip.inc pf_fa_launch): the same bits."""
+    from pass 2 or taken again; prefill.hip pf_fa_launch): the same bits."""
     L = llmi.lib()
     old = L.llmi_test_option(b"pf_fa_cfg", cfg)
     try:

@@ -1,6 +1,6 @@
 """Batched-prefill attention (llmi_pf_attention) on the edges of its kernels' own loops:
 the tiled FP64-MFMA kernel k_pf_fa (mode 0) and the LDS kernels k_pf_attn_g / k_pf_attn
-(modes 1, 2), csrc/prefill.hip.inc.  Every output is bit-identical (uint32 views) to the
+(modes 1, 2), csrc/prefill.hip.  Every output is bit-identical (uint32 views) to the
 oracle's rows (tests/pf_attention_cases.py: position-indexed data sets, one table of
 reference rows each; tests/test_pf_attention_inputs.py proves on the CPU what these inputs
 see).  `out` carries guard rows after row T - 1 that must come back unchanged, and every

@@ -1,4 +1,4 @@
-"""Batched MFMA prefill (prefill.hip.inc) through the C ABI.
+"""Batched MFMA prefill (prefill.hip) through the C ABI.
 
 The prompt's leading tokens run through every layer as one launch per op over all of
 them: q8 activations x quantized weights on v_mfma_f32_16x16x32_f16 (exact integer sums

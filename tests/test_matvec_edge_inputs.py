@@ -5,7 +5,7 @@ The saturated blocks are decoded here with plain numpy integer code (written fro
 block formats, independent of the oracle) and the integer block sums of ggml's generic
 dot are formed from them: per 256-block and residue l, aux32[l] = sum over the elements e
 = l (mod 8) of scale(e) * q(e) * a(e); per Q8_0 block, sumi = sum q(e) * a(e).  They must
-sit exactly on the bounds the kernels' exactness argument names (prefill.hip.inc header):
+sit exactly on the bounds the kernels' exactness argument names (prefill.hip header):
   Q4_K  15 * 63 * 127 * 32 =  3 840 480
   Q5_K  31 * 63 * 127 * 32 =  7 936 992
   Q6_K  32 * 128 * 127 * 32 = 16 646 144   (variant 0; 0.8 % below 2^24)

@@ -6,7 +6,7 @@ without a GPU:
   * the `range` regime reaches what it claims, counted per row and head through the
     restatement: e that are f32 subnormals, e zeroed by the exp's cut-off and e just above
     it (one float32 step on each side), p that are f16 subnormals, p = 0 with e > 0;
-  * pf_expf (k_pf_fa's exp, csrc/prefill.hip.inc: llmi_expf with the 2^n scaling as one
+  * pf_expf (k_pf_fa's exp, csrc/prefill.hip: llmi_expf with the 2^n scaling as one
     ldexp) restated with a correctly rounded ldexp equals llmi_expf's restatement on EVERY
     float32 in [-104.5, -87] and [88, 89.5] -- the claim of the kernel's comment;
   * every mistake of pf_attention_cases.VARIANTS changes the result of a named case.
