@@ -218,6 +218,18 @@ bool llama_kv_self_seq_rm(struct llama_context* ctx, llama_seq_id seq_id, llama_
  * context, a sequence outside 0..n_seq_max-1, seq_src == seq_dst, p1 beyond seq_src's past,
  * p0 beyond seq_dst's past (a hole), p0 >= p1 > 0. */
 bool llama_kv_self_seq_cp(struct llama_context* ctx, llama_seq_id seq_src, llama_seq_id seq_dst, llama_pos p0, llama_pos p1);
+/* Context shift, as llama-server does it when a slot reaches its context: upstream's
+ * seq_rm(n_keep, n_keep + n_discard) + seq_add(n_keep + n_discard, past, -n_discard) + the
+ * K-shift graph, in one launch (k_kv_shift).  The first n_keep positions of seq_id stay, the
+ * next n_discard are dropped, the rest [n_keep + n_discard, past) slide down by n_discard in
+ * place: K rows with their rotated dims re-rotated by -n_discard positions (f16 in, f32
+ * rotation, f16 out), V and the token history bit for bit.  The sequence's past becomes past -
+ * n_discard, so the next decode, single or batched, runs at the new position; the positions
+ * above it keep stale rows, which no step reads.  n_keep + n_discard == past moves nothing (a
+ * truncation).  Synchronises before it returns.  false, llmi_last_error() naming the argument
+ * and nothing changed: a null context, a sequence outside 0..n_seq_max-1, n_keep < 0,
+ * n_discard < 1, n_keep + n_discard > past. */
+bool llmi_kv_self_seq_shift(struct llama_context* ctx, llama_seq_id seq_id, int32_t n_keep, int32_t n_discard);
 /* upstream llama_memory_seq_pos_max: last position held by seq_id, -1 if empty */
 int32_t llmi_seq_pos_max(const struct llama_context* ctx, llama_seq_id seq_id);
 
@@ -586,6 +598,20 @@ int32_t llmi_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
 int32_t llmi_kv_seq_copy(int32_t n_planes, int32_t head_dim, int32_t n_ctx, int32_t p0, int32_t p1,
                          const uint16_t* kc_src, const uint16_t* vc_src, const int32_t* hist_src,
                          uint16_t* kc_dst, uint16_t* vc_dst, int32_t* hist_dst, double* usec);
+/* k_kv_shift alone (llmi_kv_self_seq_shift's launch) over device pointers, on the null stream,
+ * synchronised: positions [n_keep + n_discard, n_past) of the caches and the history move
+ * down by n_discard in place.  K, V, hist as llmi_kv_seq_copy's; rope_dev the RoPE table f32
+ * [n_ctx][n_rot / 2][cos, sin], of which row n_discard is read: with (c, s) = its entry i, the
+ * K pair (x0, x1) = dims (2i, 2i + 1) becomes (f16(x0*c + x1*s), f16(x1*c - x0*s)), f32
+ * products and sums, each rounded; dims from n_rot up, V and hist move bit for bit.  Nothing
+ * below n_keep or from n_past - n_discard up is written.  usec (optional): the launch's
+ * event-timed device microseconds (0 for an empty tail, which launches nothing).  < 0 before
+ * any device call, llmi_last_error() naming the argument: a null or misaligned pointer
+ * (16 bytes; the table 8), n_planes <= 0, head_dim other than 64 or 128, n_rot odd or outside
+ * 0..head_dim, n_ctx no positive multiple of 8, n_keep < 0, n_discard < 1, anything other than
+ * n_keep + n_discard <= n_past <= n_ctx.  0 on success. */
+int32_t llmi_kv_shift(int32_t n_planes, int32_t head_dim, int32_t n_rot, int32_t n_ctx, int32_t n_keep, int32_t n_discard,
+                      int32_t n_past, const float* rope_dev, uint16_t* kc, uint16_t* vc, int32_t* hist, double* usec);
 /* k_embd_rows / k_embd_mean alone (the embeddings launch of llama_decode) over device
  * pointers, on the null stream, synchronised.  x_dev [n_tok][ldx] f32 holds the final hidden
  * states of tokens t0 .. t0 + n_tok - 1 of a sequence of n_total tokens, norm_w_dev [n_embd]

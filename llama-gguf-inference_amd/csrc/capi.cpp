@@ -690,6 +690,30 @@ bool llama_kv_self_seq_cp(struct llama_context* ctx, llama_seq_id seq_src, llama
     API_CATCH(false)
 }
 
+bool llmi_kv_self_seq_shift(struct llama_context* ctx, llama_seq_id seq_id, int32_t n_keep, int32_t n_discard) {
+    API_TRY
+    const std::string who = "llmi_kv_self_seq_shift: ";
+    if (!ctx) { set_err(who + "ctx is a null pointer"); return false; }
+    Context& c = ctx->c;
+    if (seq_id < 0 || seq_id >= c.n_seq) { set_err(who + "seq_id out of range (n_seq_max)"); return false; }
+    const int past = seq_past_of(c, seq_id);
+    if (n_keep < 0) { set_err(who + "n_keep is negative"); return false; }
+    if (n_discard < 1) { set_err(who + "n_discard must be at least 1"); return false; }
+    if ((long long)n_keep + n_discard > past) { set_err(who + "n_keep + n_discard beyond the sequence's past"); return false; }
+    std::string err;
+    bool ok = context_seq_shift(c, seq_id, n_keep, n_discard, past, err);
+    if (ok) {
+        const hipError_t e = hipStreamSynchronize(c.stream);
+        if (e != hipSuccess) { err = hip_err(e); ok = false; }
+    }
+    if (!ok) { set_err(who + err); return false; }
+    // as a tail removal: the sequence's StepState stays, the next call sets token and
+    // position from the host (single step, batched step and prefill alike)
+    set_seq_past(c, seq_id, past - n_discard);
+    return true;
+    API_CATCH(false)
+}
+
 int32_t llmi_seq_pos_max(const struct llama_context* ctx, llama_seq_id seq_id) {
     if (!ctx || seq_id < 0 || seq_id >= ctx->c.n_seq) return -1;
     return seq_past_of(ctx->c, seq_id) - 1;

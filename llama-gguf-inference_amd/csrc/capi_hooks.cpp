@@ -914,6 +914,43 @@ int32_t llmi_kv_seq_copy(int32_t n_planes, int32_t head_dim, int32_t n_ctx, int3
     API_CATCH(-5)
 }
 
+// k_kv_shift alone over the caller's device memory (llmi_kv_self_seq_shift's launch), with the
+// caller's RoPE table.  Every refusal comes before the first device call.
+int32_t llmi_kv_shift(int32_t n_planes, int32_t head_dim, int32_t n_rot, int32_t n_ctx, int32_t n_keep, int32_t n_discard,
+                      int32_t n_past, const float* rope_dev, uint16_t* kc, uint16_t* vc, int32_t* hist, double* usec) {
+    API_TRY
+    const std::string who = "llmi_kv_shift: ";
+    const struct { const char* field; const void* p; size_t align; } ptrs[] = {
+        {"rope_dev", rope_dev, 8}, {"kc", kc, 16}, {"vc", vc, 16}, {"hist", hist, 4}};
+    for (const auto& f : ptrs) {
+        if (!f.p) { set_err(who + f.field + " is a null pointer"); return -1; }
+        if ((uintptr_t)f.p % f.align) { set_err(who + f.field + " is misaligned"); return -1; }
+    }
+    if (n_planes <= 0) { set_err(who + "n_planes must be positive"); return -1; }
+    if (head_dim != 64 && head_dim != 128) { set_err(who + "head_dim must be 64 or 128"); return -1; }
+    if (n_rot < 0 || n_rot % 2 || n_rot > head_dim) { set_err(who + "n_rot must be even and within 0..head_dim"); return -1; }
+    if (n_ctx <= 0 || n_ctx % 8) { set_err(who + "n_ctx must be a positive multiple of 8"); return -1; }
+    if (n_keep < 0) { set_err(who + "n_keep is negative"); return -1; }
+    if (n_discard < 1) { set_err(who + "n_discard must be at least 1"); return -1; }
+    if (n_past > n_ctx) { set_err(who + "n_past beyond n_ctx"); return -1; }
+    if ((long long)n_keep + n_discard > n_past) { set_err(who + "n_keep + n_discard beyond n_past"); return -1; }
+    KvShiftArgs a;
+    a.kc = kc; a.vc = vc; a.hist = hist; a.rope = rope_dev;
+    a.n_planes = n_planes; a.head_dim = head_dim; a.n_rot = n_rot; a.n_ctx = n_ctx;
+    a.n_keep = n_keep; a.n_discard = n_discard; a.n_past = n_past;
+    if (kv_shift_check(a) != hipSuccess) { set_err(who + "n_planes * head_dim too large"); return -1; }
+    const int cap = hook_grid_cap();
+    if (cap <= 0) { set_err(who + "device query failed"); return -2; }
+    HipObjs h;
+    if (usec) *usec = 0.0;
+    auto launch = [&] { return launch_kv_shift(a, cap, nullptr); };
+    hipError_t e = usec && n_keep + n_discard < n_past ? time_launch(h, launch, *usec) : launch();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_err(who + hip_err(e)); return -3; }
+    return 0;
+    API_CATCH(-5)
+}
+
 // k_embd_rows / k_embd_mean alone over the caller's device memory (the launch llama_decode
 // makes per prefill chunk and decode step in embeddings mode).  Every refusal comes before
 // the first device call, so a machine without a GPU can ask for them.

@@ -168,6 +168,28 @@ void context_clear(Context& c) {
     c.n_past = 0;
 }
 
+bool context_seq_shift(Context& c, int s, int n_keep, int n_discard, int n_past, std::string& err) {
+    const HParams& hp = c.m->hp;
+    KvShiftArgs a;
+    a.kc = c.kc0 + (size_t)s * c.kv_seq_elems;
+    a.vc = c.vc0 + (size_t)s * c.kv_seq_elems;
+    a.hist = c.hist0 + (size_t)s * c.n_ctx;
+    a.rope = c.rope;
+    a.n_planes = hp.n_layer * hp.n_head_kv;
+    a.head_dim = hp.head_dim;
+    a.n_rot = hp.n_rot;
+    a.n_ctx = c.n_ctx;
+    a.n_keep = n_keep;
+    a.n_discard = n_discard;
+    a.n_past = n_past;
+    (void)hipSetDevice(c.device);
+    (void)hipGetLastError();
+    const hipError_t e = launch_kv_shift(a, c.max_blocks, c.stream);
+    if (e == hipErrorNotSupported) err = "unsupported cache shape (head_dim 64 or 128, an even n_rot)";
+    else if (e != hipSuccess) err = hip_err(e);
+    return e == hipSuccess;
+}
+
 void context_fault_readback(Context& c) {
     (void)hipMemcpyAsync(c.fault_host, c.fault_dev, 4, hipMemcpyDeviceToHost, c.stream);
 }

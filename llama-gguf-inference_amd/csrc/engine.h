@@ -252,6 +252,9 @@ void context_select_seq(Context& c, int s);
 void context_clear(Context& c);
 // clear one sequence's KV cache, history and state
 void context_clear_seq(Context& c, int s);
+// context shift (k_kv_shift, on c.stream, no synchronisation): sequence s's positions
+// [n_keep + n_discard, n_past) move down by n_discard, K re-rotated; the caller sets its past
+bool context_seq_shift(Context& c, int s, int n_keep, int n_discard, int n_past, std::string& err);
 // enqueue the device fault word's read-back (before the call's stream sync) ...
 void context_fault_readback(Context& c);
 // ... and after the sync: false (err set, word re-armed) if an in-kernel wait gave up

@@ -474,6 +474,28 @@ bool kv_seq_cp_ok(const KvCopyArgs& a);
 // max_blocks: the context's matvec grid cap (mv_grid_cap); the grid is sized from it
 hipError_t launch_kv_seq_cp(const KvCopyArgs& a, int max_blocks, hipStream_t stream);
 
+// Context shift on the device (kvshift.hip, k_kv_shift): one sequence's positions [n_keep +
+// n_discard, n_past) move down by n_discard in place, in one launch: K rows [n_planes][n_ctx]
+// [head_dim] (their first n_rot dims rotated by -n_discard positions with row n_discard of
+// `rope`, the QKV epilogue's table [n_ctx][n_rot/2][cos,sin]; the rest bit for bit), the
+// transposed V rows [n_planes][head_dim][n_ctx] and the token history [n_ctx] bit for bit.
+// Positions below n_keep and from n_past - n_discard up are not written (the latter are stale).
+constexpr int kKvShiftChunk = 256;  // positions a workgroup reads before it writes (kvshift.hip)
+struct KvShiftArgs {
+    uint16_t *kc = nullptr, *vc = nullptr;
+    int32_t* hist = nullptr;
+    const float* rope = nullptr;
+    int n_planes = 0, head_dim = 0, n_rot = 0, n_ctx = 0;
+    int n_keep = 0, n_discard = 0, n_past = 0;
+};
+// hipErrorNotSupported: head_dim other than 64 / 128, n_ctx no multiple of 8, n_rot odd or
+// beyond head_dim; hipErrorInvalidValue: a null or misaligned pointer, anything other than 0 <=
+// n_keep, 1 <= n_discard, n_keep + n_discard <= n_past <= n_ctx
+hipError_t kv_shift_check(const KvShiftArgs& a);
+// max_blocks: the context's matvec grid cap (mv_grid_cap); the grid is sized from it.  An
+// empty tail (n_keep + n_discard == n_past) launches nothing.
+hipError_t launch_kv_shift(const KvShiftArgs& a, int max_blocks, hipStream_t stream);
+
 // Embeddings on the device (embd.hip): result_norm of the final hidden states, y =
 // (x*scale)*w with the logits prologue's scale (mv_norm_scale), and upstream's pooling over
 // the tokens of one sequence (enum llama_pooling_type; RANK is not taken).  A call covers

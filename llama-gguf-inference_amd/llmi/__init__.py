@@ -388,6 +388,23 @@ def kv_seq_copy(n_planes: int, head_dim: int, n_ctx: int, p0: int, p1: int, kc_s
     return us.value
 
 
+def kv_shift(n_planes: int, head_dim: int, n_rot: int, n_ctx: int, n_keep: int, n_discard: int, n_past: int, rope: int,
+             kc: int, vc: int, hist: int) -> float:
+    """llmi_kv_shift: k_kv_shift alone (Context.seq_shift's launch) over device addresses:
+    positions [n_keep + n_discard, n_past) of the K cache [n_planes][n_ctx][head_dim] f16, the
+    transposed V cache and the history [n_ctx] int32 move down by n_discard in place, the K
+    rows' first n_rot dims rotated back by row n_discard of the table rope f32 [n_ctx][n_rot / 2]
+    [cos, sin].  Returns the launch's event-timed device microseconds (0.0 for an empty tail);
+    bad arguments raise before any device call."""
+    us = C.c_double()
+    vp = lambda a: C.c_void_p(int(a)) if a else None  # noqa: E731
+    r = lib().llmi_kv_shift(int(n_planes), int(head_dim), int(n_rot), int(n_ctx), int(n_keep), int(n_discard), int(n_past),
+                            vp(rope), vp(kc), vp(vc), vp(hist), C.byref(us))
+    if r != 0:
+        raise LlmiError(f"llmi_kv_shift returned {r}: {last_error()}")
+    return us.value
+
+
 def embd_pool(x_dev: int, ldx: int, n_tok: int, n_embd: int, norm_w_dev: int, eps: float, pooling: int, n_total: int,
               t0: int, acc_dev: int, out_dev: int) -> float:
     """llmi_embd_pool: k_embd_rows / k_embd_mean alone (llama_decode's embeddings launch) over
@@ -631,6 +648,14 @@ class Context:
         device (p1 < 0: all src holds); dst's past becomes p1.  False (last_error() says why) for
         a bad sequence, src == dst, a range src does not hold or one that would leave a hole."""
         return bool(lib().llama_kv_self_seq_cp(self._h, int(src), int(dst), int(p0), int(p1)))
+
+    def seq_shift(self, seq: int, n_keep: int, n_discard: int) -> bool:
+        """llmi_kv_self_seq_shift (context shift): sequence seq keeps its first n_keep
+        positions, drops the next n_discard and slides the rest down on the device, K re-rotated
+        for the new positions; its past shrinks by n_discard.  False (last_error() names the
+        argument) for a bad sequence, n_keep < 0, n_discard < 1 or n_keep + n_discard beyond
+        the sequence's past."""
+        return bool(lib().llmi_kv_self_seq_shift(self._h, int(seq), int(n_keep), int(n_discard)))
 
     def seq_pos_max(self, seq: int) -> int:
         return int(lib().llmi_seq_pos_max(self._h, int(seq)))

@@ -200,6 +200,7 @@ SIGNATURES = {
                                        _P, _P, C.POINTER(C.c_double)]),
     "llama_kv_self_seq_rm": (C.c_bool, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "llama_kv_self_seq_cp": (C.c_bool, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "llmi_kv_self_seq_shift": (C.c_bool, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "llmi_seq_pos_max": (C.c_int32, [_P, C.c_int32]),
     "llmi_model_upload_s": (C.c_double, [_P]),
     "llmi_last_step_stats": (None, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -220,6 +221,8 @@ SIGNATURES = {
     "llmi_attention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32]),
     "llmi_kv_seq_copy": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P,
                                      C.POINTER(C.c_double)]),
+    "llmi_kv_shift": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                  C.POINTER(C.c_double)]),
     "llama_set_embeddings": (None, [_P, C.c_bool]),
     "llmi_set_pooling_type": (C.c_int32, [_P, C.c_int32]),
     "llama_pooling_type": (C.c_int32, [_P]),

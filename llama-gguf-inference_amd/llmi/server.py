@@ -71,6 +71,15 @@ usage.prompt_tokens_details.cached_tokens (native /completion: tokens_cached) an
 replica's /health entry the totals prompt_tokens and cached_tokens; among equally loaded
 replicas a request goes to the one that holds the longest prefix of its prompt.
 
+Context shift (llama-server's; opt-in here: `--context-shift`): a slot whose next token does
+not fit its context while it generates keeps its first n_keep positions (the request's
+`n_keep`, default 0, -1 the whole prompt, at most n_ctx - 4; plus one where the vocabulary adds
+BOS), drops the next n_discard = (n_past - n_keep) / 2 and slides the rest down on the device
+with the K rows re-rotated (llmi_kv_self_seq_shift, one launch); the slot's prompt-cache entry
+is edited the same way, and the response says `truncated: true`.  Without the flag nothing
+changes: generation ends at the context's size.  A prompt longer than the context is refused
+either way.
+
 Embeddings are opt-in, as llama-server's: `--embeddings` (or `--embedding`, LLMI_EMBEDDINGS=1)
 and `--pooling none|mean|cls|last` (default: the model's GGUF pooling_type, else none).  Then
 
@@ -157,6 +166,7 @@ class Vocab:
                 self.by_text.setdefault(t, i)
         self.max_len = max((len(t) for t in self.by_text), default=1)
         self.eog = {eos}
+        self.add_bos = bos >= 0  # llama_vocab_get_add_bos: tokenize() puts BOS first
 
     @property
     def n_vocab(self) -> int:
@@ -226,6 +236,7 @@ class TextCodec:
         self.eog = {tok.eos} | {tok.by_text[t] for t in self.EOG_TEXTS
                                 if t in tok.by_text and tok.types[tok.by_text[t]] == T.CONTROL}
         self.eog.discard(-1)
+        self.add_bos = bool(getattr(tok, "add_bos", False)) and tok.bos >= 0  # llama_vocab_get_add_bos
 
     @property
     def n_vocab(self) -> int:
@@ -263,13 +274,17 @@ class Request:
     `stop`: strings that end the generation (checked on the detokenized output).
     `n_top` >= 0: every token comes with its log-probability entry (host_logprob_entry's
     shape) in `lp`, parallel to `out`.  `cached`: how many of the prompt's positions the
-    replica's prompt cache supplied (set at admission)."""
+    replica's prompt cache supplied (set at admission).  `n_keep`: the positions a context
+    shift keeps (llama-server's field; -1: the whole prompt); `truncated`: one took place."""
 
     def __init__(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
                  sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None, n_top: int = -1,
-                 cache_prompt: bool = True):
+                 cache_prompt: bool = True, n_keep: int = 0):
         self.prompt, self.max_tokens, self.ignore_eos = list(prompt), max_tokens, ignore_eos
         self.n_top = n_top
+        self.n_keep = n_keep
+        self.truncated = False
+        self.shifted = 0                  # positions context shifts have discarded: token i of prompt + out sits at i - shifted
         self.cache_prompt = cache_prompt  # False: the whole prompt is prefilled (llama-server's field)
         self.cached = 0                   # prompt positions served from the replica's prompt cache
         self.lp: list[tuple] = []
@@ -338,8 +353,13 @@ class Replica:
     (cache_prompt) it keeps what each sequence holds and prefills only what a prompt adds."""
 
     def __init__(self, idx: int, ctx, slots: int, eog: set, chunk: int, n_ctx: int, device: int = 0,
-                 detok: Optional[Callable[[list[int]], str]] = None, cache_prompt: bool = False):
+                 detok: Optional[Callable[[list[int]], str]] = None, cache_prompt: bool = False,
+                 context_shift: bool = False, add_bos: bool = False):
         self.idx, self.ctx, self.slots, self.eog, self.chunk, self.n_ctx = idx, ctx, slots, eog, chunk, n_ctx
+        # context shift (--context-shift): a sequence that reaches n_ctx while generating drops
+        # half of what follows its first n_keep positions (Context.seq_shift) and goes on
+        self.context_shift = context_shift and hasattr(ctx, "seq_shift")
+        self.add_bos = add_bos
         self.device = device
         self.detok = detok
         self.pending: "queue.Queue[Request]" = queue.Queue()
@@ -406,14 +426,29 @@ class Replica:
         request's end are not part of it."""
         if not self.cache_prompt:
             return
-        n = min(r.pos, len(r.prompt) + len(r.out)) - len(r.prompt)
+        n = min(r.pos + r.shifted, len(r.prompt) + len(r.out)) - len(r.prompt)
         with self.lock:
             h = self.held[r.seq]
-            h += r.out[len(h) - len(r.prompt):n]
+            h += r.out[len(h) + r.shifted - len(r.prompt):n]
 
     def _forget(self, seq: int) -> None:
         with self.lock:
             self.held[seq] = []
+
+    def _shift(self, r: Request) -> None:
+        """llama-server's context shift for a sequence whose next token does not fit: keep
+        n_keep positions, discard half of the rest, slide what remains down (K re-rotated on
+        the device) and edit the sequence's token list the same way."""
+        n_keep = r.n_keep if r.n_keep >= 0 else len(r.prompt)
+        n_keep = min(self.n_ctx - 4, n_keep) + (1 if self.add_bos else 0)
+        n_discard = (r.pos - n_keep) // 2
+        if not self.ctx.seq_shift(r.seq, n_keep, n_discard):
+            raise RuntimeError(f"context shift refused (n_keep {n_keep}, n_discard {n_discard}, n_past {r.pos})")
+        with self.lock:
+            del self.held[r.seq][n_keep:n_keep + n_discard]
+        r.pos -= n_discard
+        r.shifted += n_discard
+        r.truncated = True
 
     def _release(self, r: Request) -> None:
         self._touch(r.seq)
@@ -480,7 +515,8 @@ class Replica:
                 seq, have = self.free.pop(), 0
                 c.seq_rm(seq)
             max_tokens = r.max_tokens
-            if len(r.prompt) + max_tokens > self.n_ctx:
+            # (with context shift a prompt that leaves room generates past n_ctx: _step shifts)
+            if len(r.prompt) + max_tokens > self.n_ctx and not (self.context_shift and len(r.prompt) < self.n_ctx):
                 max_tokens = max(0, self.n_ctx - len(r.prompt))
             r.max_tokens = max_tokens
             if not r.prompt or max_tokens <= 0:
@@ -569,6 +605,11 @@ class Replica:
         k = max(1, min(self.chunk, min(r.max_tokens - len(r.out) for r in batch)))
         if any(r.stop for r in batch):
             k = min(k, 4)  # stop strings are checked between decode calls
+        if self.context_shift:
+            for r in batch:
+                if r.pos >= self.n_ctx:
+                    self._shift(r)
+            k = min(k, min(self.n_ctx - r.pos for r in batch))  # no call runs past the context
         c = self.ctx
         t0 = time.perf_counter()
         # a request that wants log-probabilities where the device cannot give them (no such
@@ -684,8 +725,10 @@ class Engine:
     def __init__(self, path: str, n_ctx: int, n_gpu_layers: int, devices: list[int], slots: int = 4,
                  chunk: int = 8, contexts=None, sampling: Optional[SamplingParams] = None, numerics: int = 0,
                  max_logprobs: int = 0, cache_prompt: bool = False, embeddings: bool = False,
-                 pooling: Optional[int] = None):
+                 pooling: Optional[int] = None, context_shift: bool = False):
         self.path, self.n_ctx, self.ngl, self.devices = path, n_ctx, n_gpu_layers, devices
+        # --context-shift: generation goes on past n_ctx (Replica._shift); off: it ends there
+        self.context_shift = bool(context_shift)
         # /v1/embeddings (--embeddings; off: the routes answer 501) and the pooling type
         # (--pooling; None: the model's own, known once the contexts exist)
         self.embeddings = bool(embeddings)
@@ -740,7 +783,8 @@ class Engine:
             eog = getattr(self.vocab, "eog", {self.vocab.eos})
             detok = getattr(self.vocab, "detokenize", None)
             self.replicas = [Replica(i, c, self.slots, eog, self.chunk, self.n_ctx,
-                                     self.devices[i] if i < len(self.devices) else i, detok, self.cache_prompt)
+                                     self.devices[i] if i < len(self.devices) else i, detok, self.cache_prompt,
+                                     self.context_shift, bool(getattr(self.vocab, "add_bos", False)))
                              for i, c in enumerate(ctxs)]
             self.load_s = time.perf_counter() - t0
             self.t_ready = time.perf_counter()
@@ -750,8 +794,8 @@ class Engine:
 
     def submit(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
                sampling: Optional[SamplingParams] = None, stop: Optional[list[str]] = None, n_top: int = -1,
-               cache_prompt: bool = True) -> Request:
-        r = Request(prompt, max_tokens, ignore_eos, sampling, stop, n_top, cache_prompt)
+               cache_prompt: bool = True, n_keep: int = 0) -> Request:
+        r = Request(prompt, max_tokens, ignore_eos, sampling, stop, n_top, cache_prompt, n_keep)
         loads = [x.load() for x in self.replicas]
         tied = [x for x, n in zip(self.replicas, loads) if n == min(loads)]
         if len(tied) > 1 and cache_prompt and self.prompt_cache:
@@ -778,10 +822,11 @@ class Engine:
 
     def run(self, prompt: list[int], max_tokens: int, ignore_eos: bool,
             on_tokens: Callable[[list[int], Optional[list[tuple]]], None], sampling: Optional[SamplingParams] = None,
-            stop: Optional[list[str]] = None, n_top: int = -1, cache_prompt: bool = True) -> Request:
+            stop: Optional[list[str]] = None, n_top: int = -1, cache_prompt: bool = True, n_keep: int = 0) -> Request:
         """Serve one request to its end, handing its tokens (and, with n_top >= 0, their logprob
-        entries) to on_tokens as they come; returns the finished Request (out, finish, lp, cached)."""
-        r = self.submit(prompt, max_tokens, ignore_eos, sampling, stop, n_top, cache_prompt)
+        entries) to on_tokens as they come; returns the finished Request (out, finish, lp, cached,
+        truncated)."""
+        r = self.submit(prompt, max_tokens, ignore_eos, sampling, stop, n_top, cache_prompt, n_keep)
         seen = 0
         while True:
             toks = r.q.get()
@@ -1063,10 +1108,13 @@ class Handler(BaseHTTPRequestHandler):
             cache_prompt = req.get("cache_prompt", True)
             if not isinstance(cache_prompt, bool):
                 raise ValueError("'cache_prompt' must be a boolean")
+            n_keep = int(req.get("n_keep", 0)) if getattr(eng, "context_shift", False) else 0
         except (ValueError, TypeError) as e:
             return self._send_json(400, _error(400, str(e), "invalid_request_error"))
         # the prompt cache is on: the engine's run() also tells how much of the prompt it served
         cache_on = bool(getattr(eng, "prompt_cache", False))
+        # context shift is on: run() takes the request's n_keep and tells whether a shift took place
+        shift_on = bool(getattr(eng, "context_shift", False))
 
         def usage(n_out: int, cached: Optional[int]) -> dict:
             u = {"prompt_tokens": len(prompt), "completion_tokens": n_out, "total_tokens": len(prompt) + n_out}
@@ -1079,12 +1127,13 @@ class Handler(BaseHTTPRequestHandler):
         created = int(time.time())
         obj = "chat.completion" if chat else "text_completion"
         if not stream:
-            entries, cached = None, None
+            entries, cached, truncated = None, None, None
             try:
-                if cache_on:
+                if cache_on or shift_on:
                     r = eng.run(prompt, max_tokens, ignore_eos, lambda _t, _e: None, sampling=sampling, stop=stop,
-                                n_top=n_top, cache_prompt=cache_prompt)
-                    ids, finish, cached = r.out, r.finish or "length", r.cached
+                                n_top=n_top, cache_prompt=cache_prompt, **({"n_keep": n_keep} if shift_on else {}))
+                    ids, finish, cached = r.out, r.finish or "length", r.cached if cache_on else None
+                    truncated = r.truncated if shift_on else None
                     entries = r.lp if n_top >= 0 else None
                 elif n_top >= 0:
                     ids, finish, entries = eng.generate_logprobs(prompt, max_tokens, ignore_eos, lambda _t, _e: None,
@@ -1114,6 +1163,8 @@ class Handler(BaseHTTPRequestHandler):
                 extra = lj
             if cached is not None and route == "/completion":
                 extra["tokens_cached"] = cached
+            if truncated is not None:
+                extra["truncated"] = truncated
             return self._send_json(200, {
                 "id": rid, "object": obj, "created": created, "model": eng.model_id, "choices": [choice],
                 "usage": usage(len(ids), cached),
@@ -1164,11 +1215,12 @@ class Handler(BaseHTTPRequestHandler):
                 chunk_of(piece)
 
         try:
-            cached = None
-            if cache_on:
+            cached, truncated = None, None
+            if cache_on or shift_on:
                 r = eng.run(prompt, max_tokens, ignore_eos, on_tokens, sampling=sampling, stop=stop, n_top=n_top,
-                            cache_prompt=cache_prompt)
-                ids, finish, cached = r.out, r.finish or "length", r.cached
+                            cache_prompt=cache_prompt, **({"n_keep": n_keep} if shift_on else {}))
+                ids, finish, cached = r.out, r.finish or "length", r.cached if cache_on else None
+                truncated = r.truncated if shift_on else None
             elif n_top >= 0:
                 ids, finish, _ = eng.generate_logprobs(prompt, max_tokens, ignore_eos, on_tokens, chunk=4,
                                                        sampling=sampling, stop=stop, n_top=n_top)
@@ -1183,7 +1235,8 @@ class Handler(BaseHTTPRequestHandler):
                     else {"index": 0, "text": "", "logprobs": None, "finish_reason": finish})
             event({"id": rid, "object": cobj, "created": created, "model": eng.model_id, "choices": [last],
                    "usage": usage(len(ids), cached), **({"tokens_cached": cached} if cached is not None and
-                                                        route == "/completion" else {})})
+                                                        route == "/completion" else {}),
+                   **({"truncated": truncated} if truncated is not None else {})})
             self.wfile.write(b"data: [DONE]\n\n")
             self.wfile.flush()
         except (BrokenPipeError, ConnectionResetError):
@@ -1227,6 +1280,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-cache-prompt", dest="cache_prompt", action="store_false",
                     help="prefill every prompt in full (the default; also LLMI_CACHE_PROMPT=0, or "
                          "cache_prompt: false in a request)")
+    ap.add_argument("--context-shift", dest="context_shift", action="store_true", default=False,
+                    help="a slot that reaches its context while generating keeps its first n_keep positions "
+                         "(the request's field), drops half of the rest and goes on; responses then report "
+                         "truncated (off by default: generation ends at the context's size)")
+    ap.add_argument("--no-context-shift", dest="context_shift", action="store_false")
     ap.add_argument("--embeddings", "--embedding", dest="embeddings", action="store_true",
                     default=os.environ.get("LLMI_EMBEDDINGS", "0") == "1",
                     help="serve /v1/embeddings (also LLMI_EMBEDDINGS=1); without it the route answers 501")
@@ -1284,7 +1342,7 @@ def main(argv=None) -> int:
     eng = Engine(args.model, args.ctx_size, args.ngl, list(range(max(1, args.replicas))), slots=args.parallel,
                  chunk=args.decode_chunk, sampling=sp, numerics=numerics_value(args.numerics),
                  max_logprobs=args.max_logprobs, cache_prompt=args.cache_prompt, embeddings=args.embeddings,
-                 pooling=POOLING_NAMES[args.pooling] if args.pooling else None)
+                 pooling=POOLING_NAMES[args.pooling] if args.pooling else None, context_shift=args.context_shift)
     srv = make_server(eng, args.host, args.port, key)
     threading.Thread(target=eng.load, daemon=True).start()
     print(f"[llmi-server] listening on {args.host}:{args.port}", file=sys.stderr, flush=True)
