@@ -65,7 +65,10 @@ struct llama_model_params {
  * decode steps unless LLMI_FA_PREFILL=1 is in the environment (opt-in, off by default,
  * read on every call: the batched prefill with k_pf_attn_fa, the same bits);
  * batched steps advance its sequences together, the flash attention of every slot in
- * one launch; up to 8192 positions. */
+ * one launch.  The default decode kernel (k_attn_fa) takes up to 8192 positions and a
+ * decode past them fails; LLMI_FA_STREAM=0 in the environment when the context is created
+ * sends longer sequences to the streamed kernel (k_attn_fa_s: the same bits, no limit but
+ * n_ctx), LLMI_FA_STREAM=1 every length. */
 #define LLMI_NUMERICS_FA 2
 
 /* upstream llama_context_params (subset) */
@@ -340,7 +343,11 @@ int32_t llmi_profile_kernels(struct llama_context* ctx, llama_token first, int32
  *                     llmi_quantize_act, llmi_step_entry,
  *                     llmi_attention, llmi_battention, llmi_pf_attention,
  *                     llmi_pf_attention_fa):
- *                     LLMI_NUMERICS_* */
+ *                     LLMI_NUMERICS_*
+ *   "fa_stream"       the flash-attention numerics' decode kernel (bit-identical): 0 k_attn_fa
+ *                     up to 8192 positions and the streamed k_attn_fa_s past them, 1 the
+ *                     streamed kernel at every length, 2 (the default; LLMI_FA_STREAM sets
+ *                     it when a context is created) k_attn_fa alone, refused past 8192 */
 int32_t llmi_test_option(const char* name, int32_t value);
 /* Algorithmic bytes of one decode step at KV length n_kv (weights + one embedding row
  * + norms + KV read/write), the numerator of achieved GB/s. */
@@ -636,6 +643,9 @@ int32_t llmi_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
  * three launches (scores, softmax, PV: past 2048 positions, or mode 3).  Host only (no
  * device call); < 0 for bad arguments. */
 int32_t llmi_attn_x86_form(int32_t kv_bound, int32_t mode);
+/* The tile of the streamed flash-attention decode kernel (k_attn_fa_s), in positions: its
+ * hand-offs fall on the multiples.  Host only. */
+int32_t llmi_fa_stream_tile(void);
 /* One batched-step attention (the batched step's launch_battention) of nt slots (1..8):
  * slot t is a sequence of n_kv[t] live positions (n_kv: HOST array of nt lengths, each
  * 1..n_ctx) with its own query q [nt][n_head*head_dim], caches kc [nt][n_head_kv][n_ctx]
@@ -670,7 +680,7 @@ int32_t llmi_pf_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, i
 /* One batched-prefill attention in the flash-attention numerics (k_pf_attn_fa, what
  * prefill_enqueue launches for a LLMI_NUMERICS_FA model under LLMI_FA_PREFILL=1):
  * arguments and layouts as llmi_pf_attention, the dot association from this thread's
- * "numerics" test option (bit LLMI_NUMERICS_X86), pos0 + T <= 8192.  Row t equals
+ * "numerics" test option (bit LLMI_NUMERICS_X86), pos0 + T <= n_ctx.  Row t equals
  * llmi_attention over n_kv = pos0 + t + 1 positions in the same association |
  * LLMI_NUMERICS_FA bit for bit.  Bad arguments are rejected before any device call.
  * Returns elapsed device microseconds (>= 0) or < 0 on error. */

@@ -140,12 +140,17 @@ __global__ __launch_bounds__(256) void k_battn_fa(BAttnArgs b, int G) { attn_fa_
 
 }  // namespace
 
+// k_attn_fa up to kFaMaxKV positions, or the streamed kernel (attnfa_stream.hip: the same
+// bits at any length), by g_fa_stream
+static bool fa_streamed(int kv_bound) { return g_fa_stream == 1 || (g_fa_stream == 0 && kv_bound > kFaMaxKV); }
+
 hipError_t launch_battention_fa(const BAttnArgs& b, int nt, int n_head, int n_head_kv, int head_dim, int kv_bound,
                                 hipStream_t s) {
     const AttnArgs& a = b.a[0];
-    if (nt < 1 || nt > kMaxBatch || n_head_kv <= 0 || n_head % n_head_kv || kv_bound > kFaMaxKV || kv_bound > a.n_ctx ||
-        a.n_ctx % 8)
+    if (nt < 1 || nt > kMaxBatch || n_head_kv <= 0 || n_head % n_head_kv || kv_bound > a.n_ctx || a.n_ctx % 8)
         return hipErrorNotSupported;
+    if (fa_streamed(kv_bound)) return launch_battention_fa_s(b, nt, n_head, n_head_kv, head_dim, s);
+    if (kv_bound > kFaMaxKV) return hipErrorNotSupported;
     const int G = n_head / n_head_kv, x86 = a.num ? 1 : 0;
     const size_t lds = (size_t)2 * kFaMaxKV * 4;
 #define LLMI_BFA(D_, X_) \
@@ -156,8 +161,9 @@ hipError_t launch_battention_fa(const BAttnArgs& b, int nt, int n_head, int n_he
 }
 
 hipError_t launch_attention_fa(const AttnArgs& a, int n_head, int n_head_kv, int head_dim, int kv_bound, hipStream_t s) {
-    if (n_head_kv <= 0 || n_head % n_head_kv || kv_bound > kFaMaxKV || kv_bound > a.n_ctx || a.n_ctx % 8)
-        return hipErrorNotSupported;
+    if (n_head_kv <= 0 || n_head % n_head_kv || kv_bound > a.n_ctx || a.n_ctx % 8) return hipErrorNotSupported;
+    if (fa_streamed(kv_bound)) return launch_attention_fa_s(a, n_head, n_head_kv, head_dim, s);
+    if (kv_bound > kFaMaxKV) return hipErrorNotSupported;
     const int G = n_head / n_head_kv, x86 = a.num ? 1 : 0;
     const size_t lds = (size_t)2 * kFaMaxKV * 4;
 #define LLMI_FA(D_, X_) \

@@ -214,6 +214,12 @@ int32_t llmi_test_option(const char* name, int32_t value) {
         if (value >= 0) g_kv_cp_unroll = value;
         return old;
     }
+    if (!strcmp(name, "fa_stream")) {  // flash-attention decode kernel (kernels.h): 0 by length, 1 streamed, 2 k_attn_fa alone
+        const int old = g_fa_stream;
+        if (value > 2) { set_err("llmi_test_option: fa_stream must be 0, 1 or 2"); return -2; }
+        if (value >= 0) g_fa_stream = value;
+        return old;
+    }
     if (!strcmp(name, "pf_attn_simple")) opt = &g_pf_attn_simple;
     else if (!strcmp(name, "mv_split_nt")) opt = &g_mv_split_nt;  // 0 auto (LLMI_MV_SPLIT_NT), 256, 512
     else if (!strcmp(name, "pf_fa_noalloc")) opt = &g_pf_fa_noalloc;
@@ -987,6 +993,9 @@ int32_t llmi_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int3
     return attn_path(n_head, n_head_kv, kv_bound, head_dim, mode);
 }
 
+// The streamed flash-attention decode kernel's tile, in positions (host only).
+int32_t llmi_fa_stream_tile(void) { return kFaStreamTile; }
+
 // The form launch_attention takes in x86 numerics (host only): k_a86_h's pass class, or 0.
 int32_t llmi_attn_x86_form(int32_t kv_bound, int32_t mode) {
     if (kv_bound <= 0 || mode < 0 || mode > 7) { set_err("llmi_attn_x86_form: bad arguments"); return -1; }
@@ -1094,8 +1103,7 @@ int32_t llmi_pf_attn_path(int32_t n_head, int32_t n_head_kv, int32_t head_dim, i
 
 double llmi_pf_attention_fa(int32_t n_head, int32_t n_head_kv, int32_t head_dim, int32_t T, int32_t pos0, int32_t n_ctx,
                             const float* q, const uint16_t* kc, const uint16_t* vc, float* out) {
-    if (!pf_attention_args_ok(n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out) || n_head / n_head_kv > 32 ||
-        pos0 + T > kFaMaxKV) {
+    if (!pf_attention_args_ok(n_head, n_head_kv, head_dim, T, pos0, n_ctx, q, kc, vc, out) || n_head / n_head_kv > 32) {
         set_err("llmi_pf_attention_fa: bad arguments");
         return -1;
     }
@@ -1158,6 +1166,7 @@ double llmi_bench_attention(int32_t n_head, int32_t n_head_kv, int32_t head_dim,
     AttnArgs a;
     a.q = q; a.out = out; a.st = st; a.n_ctx = n_ctx; a.scale = 1.0f / sqrtf((float)head_dim);
     a.num = t_hook_numerics & NUMERICS_X86;
+    a.fa = (t_hook_numerics & NUMERICS_FA) ? 1 : 0;
     attn_bind_scratch(a, scores, n_head, n_ctx);
     if (trace_dev) {  // one traced eager launch on a cold layer (LLMI_EXP_TRACE builds)
         for (int l = 0; l + 1 < nl; ++l) {

@@ -64,6 +64,9 @@ bool context_init(Model* m, int n_ctx, bool use_graphs, int n_seq, Context& c, s
     {
         const char* e = getenv("LLMI_ATTN_MODE");
         set_attn_mode(e ? atoi(e) : 0);
+        // flash-attention decode kernel (kernels.h g_fa_stream); unset leaves the process setting
+        const char* f = getenv("LLMI_FA_STREAM");
+        if (f && atoi(f) >= 0 && atoi(f) <= 2) g_fa_stream = atoi(f);
     }
     c.use_graphs = use_graphs;
     HIPC(hipSetDevice(m->device));

@@ -37,7 +37,9 @@ struct Layer {
 //   + NUMERICS_FA (bit 1 of llama_model_params.numerics): decode attention in ggml's CPU
 //     flash-attention numerics (attnfa.hip) in the association of bit 0; a batched step
 //     runs that attention for all its slots in one launch, and prompts go through the
-//     batched prefill only with LLMI_FA_PREFILL=1 (else as decode steps)
+//     batched prefill only with LLMI_FA_PREFILL=1 (else as decode steps).  k_attn_fa takes
+//     up to kFaMaxKV positions; LLMI_FA_STREAM (kernels.h g_fa_stream) brings in the
+//     streamed kernel, which takes what the context holds
 enum : int { NUMERICS_GENERIC = 0, NUMERICS_X86 = 1, NUMERICS_FA = 2 };
 
 struct Model {
@@ -290,7 +292,8 @@ bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& er
 // only with LLMI_FA_PREFILL=1, read on every call)
 bool prefill_supported(const Model& m);
 // positions the batched prefill's attention reaches: the context when the tiled kernel
-// (k_pf_fa) takes the model's heads, else the LDS kernels' pf_max_kv()
+// (k_pf_fa) takes the model's heads, else the LDS kernels' pf_max_kv(); flash-attention
+// numerics: as far as the decode kernel in use follows (kFaMaxKV, or the context)
 int prefill_max_kv(Context& c);
 // run tokens [0, n) at positions pos0.. through every layer as batched launches (KV
 // cache written, no logits); enqueued on c.stream, no synchronisation

@@ -352,8 +352,18 @@ LongGeo attn_long_geo(int kv_bound);
 // arm (or with nullptrs disarm) per-op kernel timing events for this thread's launches
 void set_launch_events(hipEvent_t start, hipEvent_t stop);
 void set_attn_mode(int mode);
-// flash-attention numerics decode attention (attnfa.hip): up to kFaMaxKV positions
+// flash-attention numerics decode attention.  k_attn_fa (attnfa.hip) keeps a score and a
+// factor per position in LDS: up to kFaMaxKV positions.  k_attn_fa_s (attnfa_stream.hip)
+// walks the keys in tiles of kFaStreamTile positions with a fixed LDS footprint: the same
+// bits at any length.  g_fa_stream picks (test option "fa_stream"; LLMI_FA_STREAM when a
+// context is created): 0 k_attn_fa up to kFaMaxKV and the streamed kernel past it, 1 the
+// streamed kernel at every length, 2 (the default) k_attn_fa alone, refused past kFaMaxKV
+// (hipErrorNotSupported).
 constexpr int kFaMaxKV = 8192;
+constexpr int kFaStreamTile = 384;
+extern int g_fa_stream;
+hipError_t launch_attention_fa_s(const AttnArgs& a, int n_head, int n_head_kv, int head_dim, hipStream_t s);
+hipError_t launch_battention_fa_s(const BAttnArgs& b, int nt, int n_head, int n_head_kv, int head_dim, hipStream_t s);
 hipError_t launch_attention_fa(const AttnArgs& a, int n_head, int n_head_kv, int head_dim, int kv_bound, hipStream_t s);
 // the batched step's flash-attention / x86 attention: every batch slot in one launch
 hipError_t launch_battention_fa(const BAttnArgs& b, int nt, int n_head, int n_head_kv, int head_dim, int kv_bound,
@@ -377,7 +387,7 @@ int pf_attn_x86_max_kv(int n_head, int n_head_kv, int head_dim);
 // launch_attention_x86's form at this KV bound and mode: k_a86_h's pass class U, 0 = three launches
 int attn_x86_form(int kv_bound, int mode);
 // flash-attention numerics prefill attention (pfattnfa.hip): T rows at pos0.., the bits of
-// T launch_attention_fa steps; pos0 + T <= kFaMaxKV, gqa <= 32 (hipErrorNotSupported)
+// T launch_attention_fa steps; pos0 + T <= n_ctx, gqa <= 32 (hipErrorNotSupported)
 hipError_t launch_pf_attn_fa(const PfAttn& a, int n_head, int head_dim, int T, hipStream_t s);
 // writes the prologue's quantized activation in ggml block form (test hook)
 hipError_t launch_quant_dump(const MVArgs& a, int act, void* out, hipStream_t stream);

@@ -26,8 +26,8 @@
 //              (stale cache entries may be NaN): they score -inf in the scan, and in the
 //              tiles that cross the diagonal every chain keeps its old value by select.
 //   state      M per pair (phase a/b waves), S per pair and y per (pair, dim) (phase c)
-// No KV-length limit of its own (launch_pf_attn_fa takes up to kFaMaxKV like the decode
-// kernel, whose results it must equal).
+// No KV-length limit of its own: launch_pf_attn_fa takes what the context holds (past
+// kFaMaxKV the decode steps that follow need the streamed decode kernel, kernels.h).
 #include "kernels.h"
 #include "launch_util.h"
 #include "mv_device.h"
@@ -329,8 +329,7 @@ __global__ __launch_bounds__(kPfaThreads) void k_pf_attn_fa(PfAttn a, int T) {
 
 hipError_t launch_pf_attn_fa(const PfAttn& a, int n_head, int head_dim, int T, hipStream_t s) {
     const int G = a.gqa;
-    if (T <= 0 || G <= 0 || G > kPfaPairs || n_head % G || a.pos0 < 0 || a.pos0 + T > a.n_ctx || a.pos0 + T > kFaMaxKV ||
-        a.n_ctx % 8)
+    if (T <= 0 || G <= 0 || G > kPfaPairs || n_head % G || a.pos0 < 0 || a.pos0 + T > a.n_ctx || a.n_ctx % 8)
         return hipErrorNotSupported;
     const int TQ = kPfaPairs / G;
     const dim3 grid(n_head / G, (T + TQ - 1) / TQ);

@@ -74,7 +74,8 @@ static bool prefill_alloc(Context& c, std::string& err) {
 int prefill_max_kv(Context& c) {
     const HParams& hp = c.m->hp;
     const int lim = pf_max_kv();
-    if (c.m->fa) return std::min(c.n_ctx, kFaMaxKV);  // k_pf_attn_fa streams the keys: no score space
+    // k_pf_attn_fa streams the keys (no score space): as far as the decode steps after it can follow
+    if (c.m->fa) return g_fa_stream == 2 ? std::min(c.n_ctx, kFaMaxKV) : c.n_ctx;
     if (c.m->numerics == NUMERICS_X86)  // k_pf_a86 keeps the G heads' scores in LDS
         return std::min(lim, pf_attn_x86_max_kv(hp.n_head, hp.n_head_kv, hp.head_dim));
     // the whole context only where the tiled kernel can run: its score scratch must exist

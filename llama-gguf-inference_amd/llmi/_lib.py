@@ -234,6 +234,7 @@ SIGNATURES = {
                                    _P, _P, C.POINTER(C.c_double)]),
     "llmi_attn_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "llmi_attn_x86_form": (C.c_int32, [C.c_int32, C.c_int32]),
+    "llmi_fa_stream_tile": (C.c_int32, []),
     "llmi_battention": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _P, _P,
                                     _P, _P]),
     "llmi_pf_attention": (C.c_double, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
