@@ -13,6 +13,7 @@
  *   Q5_K 176 B {f16 d, f16 dmin, u8 scales[12], u8 qh[32], u8 qs[128]}
  *   Q6_K 210 B {u8 ql[128], u8 qh[64], i8 scales[16], f16 d}
  *   Q8_0  34 B {f16 d, i8 qs[32]}
+ *   Q3_K 110 B {u8 hmask[32], u8 qs[64], u8 scales[12], f16 d}
  */
 #ifndef LLMI_SYNTH_H
 #define LLMI_SYNTH_H
@@ -20,7 +21,7 @@
 #include "llmi_math.h"
 
 enum {
-    LLMI_T_F32 = 0, LLMI_T_F16 = 1, LLMI_T_Q8_0 = 8, LLMI_T_Q4_K = 12,
+    LLMI_T_F32 = 0, LLMI_T_F16 = 1, LLMI_T_Q8_0 = 8, LLMI_T_Q3_K = 11, LLMI_T_Q4_K = 12,
     LLMI_T_Q5_K = 13, LLMI_T_Q6_K = 14, LLMI_T_Q8_K = 15
 };
 
@@ -29,6 +30,7 @@ enum {
 #define LLMI_SYN_D_Q5K 3.79e-5f  /* std(d*sc*q - 15.5*d*m) = 527.2*d */
 #define LLMI_SYN_D_Q6K 2.93e-5f  /* std(d*sc*(q-32)) = 682.9*d */
 #define LLMI_SYN_D_Q80 2.73e-4f  /* std(d*q), q uniform in [-127,127] = 73.3*d */
+#define LLMI_SYN_D_Q3K 4.61e-4f  /* std(d*(sc-32)*q), sc in [0,63], q in [-4,3] = 43.3*d */
 
 /* Writes one quantized block of `type` (block index `bi` inside tensor `tensor`). */
 LLMI_HD void llmi_synth_block(int type, uint64_t seed, uint64_t tensor, uint64_t bi, uint8_t* out) {
@@ -49,6 +51,10 @@ LLMI_HD void llmi_synth_block(int type, uint64_t seed, uint64_t tensor, uint64_t
         for (int k = 0; k < 16; ++k) out[192 + k] = (uint8_t)(int8_t)((int)(LLMI_SB(192 + k) & 127u) - 64);
         uint16_t hd = llmi_f2h(LLMI_SYN_D_Q6K * jit);
         out[208] = (uint8_t)hd; out[209] = (uint8_t)(hd >> 8);
+    } else if (type == LLMI_T_Q3_K) {
+        for (int k = 0; k < 108; ++k) out[k] = LLMI_SB(k);              /* hmask, qs, scales */
+        uint16_t hd = llmi_f2h(LLMI_SYN_D_Q3K * jit);
+        out[108] = (uint8_t)hd; out[109] = (uint8_t)(hd >> 8);
     } else if (type == LLMI_T_Q8_0) {
         uint16_t hd = llmi_f2h(LLMI_SYN_D_Q80 * jit);
         out[0] = (uint8_t)hd; out[1] = (uint8_t)(hd >> 8);

@@ -74,7 +74,7 @@ double replay_us(HipObjs& h, int n, int per_replay) {
 bool head_shape_ok(int n_head, int n_head_kv, int head_dim) {
     return n_head > 0 && n_head_kv > 0 && n_head % n_head_kv == 0 && (head_dim == 64 || head_dim == 128);
 }
-bool weight_type_ok(int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0; }
+bool weight_type_ok(int t) { return needs_repack(t); }
 int hook_grid_cap() {  // the matvec grid cap a context of the current device launches with
     int dev = 0;
     (void)hipGetDevice(&dev);

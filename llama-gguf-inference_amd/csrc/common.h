@@ -15,6 +15,8 @@
 //   Q6_K  A: ql 128 B/unit   H: [row][4][unit][16 B] 2-bit highs (XOR 2)
 //         S: scales 16 B/unit (native order)   D: fp16 d 2 B/unit
 //   Q8_0  A: qs 256 B/unit (part p = 32-block p/2, half p%2)   D: 8 fp16 d = 16 B/unit
+//   Q3_K  A: 2-bit lows 64 B/unit: [row][4][unit][16 B]   H: [row][2][unit][16 B] high bits
+//         (inverted)   S: the 12 packed 6-bit scale bytes per unit   D: fp16 d 2 B/unit
 //   F32/F16 plain (A).
 // K-quant parts are in RESIDUE ORDER: part p = 2c + k of chunk c (64 weights: low
 // nibbles = weights 64c + t, high nibbles = 64c + 32 + t of native qs[32c + t]), byte
@@ -24,6 +26,15 @@
 // weights, hi word: high-nibble weights; bit 4l + i as above), chunks 2h, 2h+1 in H
 // part h.  Q6_K high bits: 16 B per chunk in H part c: dword 2*hi + k, byte i, bits 2m
 // (XOR 2, so v_perm maps them to the signed high part of q - 32).
+// Q3_K (generic numerics only) keeps the same residue order three bits deep.  Chunk c is A
+// part c: dword m, byte i, bits [2j, 2j + 1] with j = 2 hi + k hold the low bits of chunk
+// element 32 hi + l + 8i, l = 4k + m -- the four 2-bit fields of a dword are the dwords m of
+// {part 2c LO, part 2c + 1 LO, part 2c HI, part 2c + 1 HI} of the activation image.  The
+// element's high bit is stored INVERTED (then (hb, lo1, lo0) is q = lo - (hmask ? 0 : 4) in
+// 3-bit two's complement) in H part c / 2, dword m, at bit ((8i + 2j + 2) mod 32) + (c & 1):
+// directly above its 2-bit field (field 3 of byte 3 wraps to bit 0), odd chunks one bit up.  So
+// (a & field mask) | ((h >> (c & 1)) & bit mask), rotated to the top of each byte, is four
+// signed bytes 32 q: three VALU per dword, no per-byte subtract (mv_device.h q3_dword).
 #pragma once
 
 #include <cstddef>
@@ -35,14 +46,14 @@ namespace llmi {
 
 enum : int {
     T_F32 = LLMI_T_F32, T_F16 = LLMI_T_F16, T_Q8_0 = LLMI_T_Q8_0,
-    T_Q4_K = LLMI_T_Q4_K, T_Q5_K = LLMI_T_Q5_K, T_Q6_K = LLMI_T_Q6_K
+    T_Q4_K = LLMI_T_Q4_K, T_Q5_K = LLMI_T_Q5_K, T_Q6_K = LLMI_T_Q6_K, T_Q3_K = LLMI_T_Q3_K
 };
 
 inline int block_elems(int t) {
     switch (t) {
         case T_F32: case T_F16: return 1;
         case T_Q8_0: return 32;
-        case T_Q4_K: case T_Q5_K: case T_Q6_K: return 256;
+        case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: return 256;
         default: return 0;
     }
 }
@@ -50,15 +61,17 @@ inline int block_bytes(int t) {
     switch (t) {
         case T_F32: return 4; case T_F16: return 2; case T_Q8_0: return 34;
         case T_Q4_K: return 144; case T_Q5_K: return 176; case T_Q6_K: return 210;
+        case T_Q3_K: return 110;
         default: return 0;
     }
 }
-inline bool is_kquant(int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K; }
+inline bool is_kquant(int t) { return t == T_Q3_K || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K; }
 inline bool type_supported(int t) { return block_bytes(t) != 0; }
 inline const char* type_name(int t) {
     switch (t) {
         case T_F32: return "f32"; case T_F16: return "f16"; case T_Q8_0: return "q8_0";
         case T_Q4_K: return "q4_K"; case T_Q5_K: return "q5_K"; case T_Q6_K: return "q6_K";
+        case T_Q3_K: return "q3_K";
         default: return "?";
     }
 }
@@ -78,7 +91,7 @@ inline size_t tensor_bytes(int t, int64_t rows, int64_t cols) {
 // the plain row-major form (RG = 1) gives R separate runs of U * 16 B.  The S and D planes
 // are row-major per unit, which is already contiguous over a group.
 inline int layout_rgs(int type, int64_t rows, int64_t cols) {
-    if (!(type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0) || cols % 256) return 0;
+    if (!(is_kquant(type) || type == T_Q8_0) || cols % 256) return 0;
     const int64_t U = cols / 256;
     int64_t lr = ((U < 64 ? U : 64) + 3) & ~(int64_t)3;
     if (lr < 4) lr = 4;
@@ -117,6 +130,11 @@ inline size_t plan_planes(DevMat& m, size_t base) {
             m.off_s = align_up(m.off_h + nblk * 64, 256);
             m.off_d = align_up(m.off_s + nblk * 16, 256);
             return m.off_d + nblk * 2;
+        case T_Q3_K:
+            m.off_h = align_up(m.off_a + nblk * 64, 256);
+            m.off_s = align_up(m.off_h + nblk * 32, 256);
+            m.off_d = align_up(m.off_s + nblk * 12, 256);
+            return m.off_d + nblk * 2;
         case T_Q8_0:
             m.off_d = align_up(m.off_a + nblk * 32, 256);
             return m.off_d + nblk * 2;
@@ -124,14 +142,15 @@ inline size_t plan_planes(DevMat& m, size_t base) {
             return m.off_a + m.bytes;
     }
 }
-inline bool needs_repack(int t) { return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0; }
+inline bool needs_repack(int t) { return is_kquant(t) || t == T_Q8_0; }
 // piece_off (mv_device.h) and the kernels' plane offsets are 32-bit: the largest plane of a
-// repacked matrix, A (128 B per K-quant block, 32 B per Q8_0 block), must end below 4 GiB.
+// repacked matrix, A (128 B per K-quant block, 64 B per Q3_K block, 32 B per Q8_0 block), must
+// end below 4 GiB.
 // rows, cols > 0.
 constexpr const char* kPlaneLimitMsg = "the matrix's quant plane reaches 4 GiB (32-bit piece offsets)";
 inline bool planes_fit_u32(int t, int64_t rows, int64_t cols) {
     if (!needs_repack(t)) return true;
-    const int64_t per_row = cols / block_elems(t) * (t == T_Q8_0 ? 32 : 128);
+    const int64_t per_row = cols / block_elems(t) * (t == T_Q8_0 ? 32 : t == T_Q3_K ? 64 : 128);
     return per_row < ((int64_t)1 << 32) && rows <= (((int64_t)1 << 32) - 1) / (per_row > 0 ? per_row : 1);
 }
 

@@ -182,6 +182,39 @@ __global__ void k_repack_kq(int type, const uint8_t* raw, uint8_t* A, uint8_t* H
                 h[4 + i] = hi;
             }
         }
+    } else if (type == T_Q3_K) {
+        // three bits deep (common.h): A part c, dword m, byte i, field j = 2 hi + k: the low bits
+        // of chunk element 32 hi + 4k + m + 8i; its high bit, inverted, in H part c / 2, dword m,
+        // bit ((8i + 2j + 2) mod 32) + (c & 1).  The even chunk's thread writes the pair's H part.
+        const uint8_t* x = raw + b * 110;
+        const uint8_t* hm = x;
+        const uint8_t* qs = x + 32;
+        auto el = [&](int j, int m, int i) { return 32 * (j >> 1) + 4 * (j & 1) + m + 8 * i; };
+        auto lo = [&](int w) -> int { return (qs[32 * (w >> 7) + (w & 31)] >> (2 * ((w >> 5) & 3))) & 3; };
+        auto hi = [&](int w) -> int { return (hm[w & 31] >> (w >> 5)) & 1; };
+        uint8_t* ap = A + piece_off((uint32_t)row, (uint32_t)c, (uint32_t)u, (uint32_t)U, 4, rgs);
+        for (int m = 0; m < 4; ++m)
+            for (int i = 0; i < 4; ++i) {
+                uint8_t v = 0;
+                for (int j = 0; j < 4; ++j) v |= (uint8_t)(lo(64 * c + el(j, m, i)) << (2 * j));
+                ap[4 * m + i] = v;
+            }
+        if ((c & 1) == 0) {
+            uint8_t* h = H + piece_off((uint32_t)row, (uint32_t)(c >> 1), (uint32_t)u, (uint32_t)U, 2, rgs);
+            for (int m = 0; m < 4; ++m) {
+                uint32_t v = 0;
+                for (int cc = 0; cc < 2; ++cc)
+                    for (int i = 0; i < 4; ++i)
+                        for (int j = 0; j < 4; ++j)
+                            v |= (uint32_t)(hi(64 * (c + cc) + el(j, m, i)) ^ 1) << (((8 * i + 2 * j + 2) & 31) + cc);
+                for (int i = 0; i < 4; ++i) h[4 * m + i] = (uint8_t)(v >> (8 * i));
+            }
+        }
+        if (c == 0) {
+            for (int i = 0; i < 12; ++i) S[b * 12 + i] = x[96 + i];
+            Dp[b * 2] = x[108];
+            Dp[b * 2 + 1] = x[109];
+        }
     } else {  // Q6_K
         const uint8_t* x = raw + b * 210;
         const uint8_t* ql = x;
@@ -306,6 +339,9 @@ static hipError_t mv_dispatch_qkv2(const MVArgs& a, dim3 grid, size_t lds, hipSt
     if (t1 == A_ && t2 == B_) return mv_qkv2_launch<NORM, A_, B_, X86>(a, sp, grid, lds, s);
     if constexpr (NORM) {
         LLMI_QKV2(T_Q4_K, T_Q6_K) LLMI_QKV2(T_Q4_K, T_Q5_K) LLMI_QKV2(T_Q5_K, T_Q6_K)
+        if constexpr (!X86) {  // Q3_K_M files: q / k in Q3_K, attn_v in Q4_K or Q5_K
+            LLMI_QKV2(T_Q3_K, T_Q4_K) LLMI_QKV2(T_Q3_K, T_Q5_K)
+        }
     }
 #undef LLMI_QKV2
     return hipErrorNotSupported;
@@ -330,6 +366,9 @@ static hipError_t mv_dispatch_type(const MVArgs& a, int epi, dim3 grid, size_t l
         case T_Q4_K: return mv_dispatch_epi<0, NORM, T_Q4_K, X86>(a, epi, grid, lds, s);
         case T_Q5_K: return mv_dispatch_epi<0, NORM, T_Q5_K, X86>(a, epi, grid, lds, s);
         case T_Q6_K: return mv_dispatch_epi<0, NORM, T_Q6_K, X86>(a, epi, grid, lds, s);
+        case T_Q3_K:
+            if constexpr (X86) return hipErrorNotSupported;  // no x86 association of Q3_K (model.cpp refuses the load)
+            else return mv_dispatch_epi<0, NORM, T_Q3_K, 0>(a, epi, grid, lds, s);
         case T_Q8_0: return mv_dispatch_epi<1, NORM, T_Q8_0, X86>(a, epi, grid, lds, s);
         default: return hipErrorInvalidValue;
     }
@@ -560,7 +599,8 @@ hipError_t launch_repack(int type, const void* raw, uint8_t* a, uint8_t* h, uint
                          int64_t cols, int rgs, int x86, hipStream_t s) {
     if (nblk <= 0) return hipSuccess;
     if (cols % 256) return hipErrorInvalidValue;
-    if (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K) {
+    if (type == T_Q3_K && x86) return hipErrorInvalidValue;  // Q3_K: generic numerics only
+    if (is_kquant(type)) {
         const int64_t thr = nblk * 4;
         hipLaunchKernelGGL(k_repack_kq, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, type, (const uint8_t*)raw, a,
                            h, sp, d, nblk, (int)(cols / 256), rgs, x86);

@@ -490,12 +490,12 @@ __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMI
 __device__ __forceinline__ uint32_t q6_hi_bytes(uint32_t sel) { return __builtin_amdgcn_perm(0xF0E01000u, 0xF0E01000u, sel); }
 
 template <int T>
-__host__ __device__ constexpr int unit_parts() { return T == T_Q8_0 ? 16 : 8; }
+__host__ __device__ constexpr int unit_parts() { return T == T_Q8_0 ? 16 : T == T_Q3_K ? 4 : 8; }
 template <int T>
-__host__ __device__ constexpr int unit_hparts() { return T == T_Q6_K ? 4 : T == T_Q5_K ? 2 : 1; }
+__host__ __device__ constexpr int unit_hparts() { return T == T_Q6_K ? 4 : (T == T_Q5_K || T == T_Q3_K) ? 2 : 1; }
 // plane bytes per unit (row strides are U times these)
 template <int T>
-__host__ __device__ constexpr uint32_t unit_abytes() { return T == T_Q8_0 ? 256u : 128u; }
+__host__ __device__ constexpr uint32_t unit_abytes() { return T == T_Q8_0 ? 256u : T == T_Q3_K ? 64u : 128u; }
 
 // byte offset of 16-B piece (row, part p, unit u) of an A / H plane with np parts per
 // unit, rows in groups of 2^rgs (common.h ROW GROUPS)
@@ -508,9 +508,9 @@ __host__ __device__ __forceinline__ uint32_t piece_off(uint32_t row, uint32_t p,
 template <int T>
 struct UnitW {
     u32x4 q[unit_parts<T>()];   // quant parts
-    u32x4 s;                    // Q4_K/Q5_K header; Q6_K 16 scales; Q8_0 eight fp16 d
-    u32x4 h[unit_hparts<T>()];  // Q5_K fifth bits (2 x 16 B); Q6_K 2-bit highs (4 x 16 B)
-    uint32_t d;                 // Q6_K fp16 d
+    u32x4 s;                    // Q4_K/Q5_K header; Q6_K 16 scales; Q8_0 eight fp16 d; Q3_K .x .y .z the 12 scale bytes
+    u32x4 h[unit_hparts<T>()];  // Q5_K fifth bits (2 x 16 B); Q6_K 2-bit highs (4 x 16 B); Q3_K inverted high bits (2 x 16 B)
+    uint32_t d;                 // Q6_K / Q3_K fp16 d
 };
 
 // Unit u of row `row` of a segment.  Loads are unconditional (callers clamp row and
@@ -526,6 +526,12 @@ __device__ __forceinline__ UnitW<T> load_unit(const Seg& sg, uint32_t row, uint3
     for (int p = 0; p < unit_parts<T>(); ++p) w.q[p] = ldw(sg.a + oa + (uint32_t)p * P);
     if constexpr (T == T_Q8_0) {
         w.s = ldw(sg.d + ru * 16);
+    } else if constexpr (T == T_Q3_K) {  // 110 B per unit: 4 + 2 parts, 12 scale bytes, d
+        w.s = u32x4{ldw4(sg.s + ru * 12), ldw4(sg.s + ru * 12 + 4), ldw4(sg.s + ru * 12 + 8), 0u};
+        const uint32_t oh = piece_off(row, 0, u, U, 2, sg.rgs);
+        w.h[0] = ldw(sg.h + oh);
+        w.h[1] = ldw(sg.h + oh + P);
+        w.d = *(const uint16_t*)(sg.d + ru * 2);
     } else {
         w.s = ldw(sg.s + ru * 16);
         if constexpr (T == T_Q5_K || T == T_Q6_K) {
@@ -563,6 +569,80 @@ template <int T>
 __host__ __device__ constexpr int unit_chains() { return T == T_Q8_0 ? 8 : 9; }  // terms per unit
 template <int ACT>
 __host__ __device__ constexpr int row_chains() { return ACT ? 1 : 9; }            // fp32 chains per row
+
+// ---- Q3_K (generic numerics only; layout: common.h) ----
+// The 12 scale bytes -> the sixteen 6-bit scales as bytes, chunk c's four sub-blocks in
+// dword c (upstream's kmask unpack), XOR 32: scale - 32 in 6-bit two's complement, which
+// q3_sc sign-extends while it extracts (one v_bfe_i32).
+__device__ __forceinline__ u32x4 q3_scales(uint32_t s0, uint32_t s1, uint32_t s2) {
+    constexpr uint32_t H = 0x30303030u, X = 0x20202020u;
+    return u32x4{((s0 & M4) | ((s2 << 4) & H)) ^ X, ((s1 & M4) | ((s2 << 2) & H)) ^ X,
+                 (((s0 >> 4) & M4) | (s2 & H)) ^ X, (((s1 >> 4) & M4) | ((s2 >> 2) & H)) ^ X};
+}
+__device__ __forceinline__ int q3_sc(uint32_t s4, int k) { return (int)(s4 << (26 - 8 * k)) >> 26; }
+// Field j of quant dword `a` with its high bits from `hs` (the H dword, shifted down one for an
+// odd chunk) -> four signed bytes 32 q: the high bit sits directly above the 2-bit field (field
+// 3: in bit 0 of the next byte, byte 3's in bit 0 of the dword), so one mask-and-merge and one
+// shift or rotate put (high, low1, low0) on bits 7..5 of each byte, whose int8 value is
+// 32 (low - 4 high), high being the inverted hmask bit.  Three VALU, j a constant after unrolling.
+__device__ __forceinline__ uint32_t q3_dword(uint32_t a, uint32_t hs, int j) {
+    const uint32_t x = (a & (M2 << (2 * j))) | (hs & (j == 3 ? M1 : 0x04040404u << (2 * j)));
+    return j == 3 ? __builtin_amdgcn_alignbit(x, x, 1) : x << (5 - 2 * j);
+}
+// The eight exact aux32[l] of a unit.  MASKED: `a` is the unit's masked activation record
+// (q6_masks_build: per part the LO dwords with bytes 2,3 / 0,1 zeroed, then the HI ones), else
+// its plain record.  Every dot is 32 x the true one: |32 q| <= 128, |a| <= 127, two live bytes:
+// |dot| <= 32512, times |scale - 32| <= 32 < 2^23 (exact 24-bit multiplies); sixteen of those per
+// l stay below 2^25, and the sum is a multiple of 32: the final shift is exact.
+template <bool MASKED, bool DZ = true>
+__device__ __forceinline__ void q3_ints(const UnitW<T_Q3_K>& w, const uint8_t* a, int (&t)[8]) {
+    const auto dz = [](uint32_t x, int y) {
+        if constexpr (DZ) return dot4z(x, y);
+        else return dot4(x, y, 0);
+    };
+    const u32x4 sc = q3_scales(w.s.x, w.s.y, w.s.z);
+#pragma unroll
+    for (int l = 0; l < 8; ++l) t[l] = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int c0 = q3_sc(sc[c], 0), c1 = q3_sc(sc[c], 1), c2 = q3_sc(sc[c], 2), c3 = q3_sc(sc[c], 3);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int p = 2 * c + k;
+            i32x4 a0, a1, a2, a3;
+            if constexpr (MASKED) {
+                a0 = *(const i32x4*)(a + 64 * p), a1 = *(const i32x4*)(a + 64 * p + 16);
+                a2 = *(const i32x4*)(a + 64 * p + 32), a3 = *(const i32x4*)(a + 64 * p + 48);
+            } else {
+                const i32x4 alo = *(const i32x4*)(a + 32 * p), ahi = *(const i32x4*)(a + 32 * p + 16);
+                a0 = alo & 0xffff, a1 = alo & (int)0xffff0000u, a2 = ahi & 0xffff, a3 = ahi & (int)0xffff0000u;
+            }
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const uint32_t hs = w.h[c >> 1][m] >> (c & 1);
+                const uint32_t wl = q3_dword(w.q[c][m], hs, k), wh = q3_dword(w.q[c][m], hs, 2 + k);
+                int v = t[4 * k + m];
+                v = __mul24(c0, dz(wl, a0[m])) + v;
+                v = __mul24(c1, dz(wl, a1[m])) + v;
+                v = __mul24(c2, dz(wh, a2[m])) + v;
+                v = __mul24(c3, dz(wh, a3[m])) + v;
+                t[4 * k + m] = v;
+            }
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 8; ++l) t[l] >>= 5;
+}
+// tm[l] = (d_w d_a) (float)aux32[l], no min chain: Q6_K's eight chains (tm[8] = +0)
+template <bool MASKED, bool DZ = true>
+__device__ __forceinline__ void q3_terms(const UnitW<T_Q3_K>& w, const uint8_t* a, float da, float (&tm)[9]) {
+    int t[8];
+    q3_ints<MASKED, DZ>(w, a, t);
+    const float d = h2f(w.d) * da;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) tm[l] = d * (float)t[l];
+    tm[8] = 0.f;
+}
 
 // The unit's terms against activation record `rec` (kRec layout): K-quants tm[l] =
 // d*(float)aux32[l] (l < 8), tm[8] = -(dmin*(float)sumi) (Q6_K: +0, there is no min
@@ -667,6 +747,8 @@ __device__ __forceinline__ void unit_terms(const UnitW<T>& w, const uint8_t* rec
 #pragma unroll
         for (int l = 0; l < 8; ++l) tm[l] = d * (float)t[l];
         tm[8] = 0.f;
+    } else if constexpr (T == T_Q3_K) {
+        q3_terms<false, DZ>(w, rec, *(const float*)(rec + kRecD), tm);
     } else {
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
@@ -1390,6 +1472,7 @@ __device__ __forceinline__ void task_any(const MA& A, const Lds& L, float* F, co
             switch (sg.type) {
                 case T_Q4_K: unit_terms<T_Q4_K>(load_unit<T_Q4_K>(sg, lu.row, lu.u, g.U), rec, tm); break;
                 case T_Q5_K: unit_terms<T_Q5_K>(load_unit<T_Q5_K>(sg, lu.row, lu.u, g.U), rec, tm); break;
+                case T_Q3_K: unit_terms<T_Q3_K>(load_unit<T_Q3_K>(sg, lu.row, lu.u, g.U), rec, tm); break;
                 default: unit_terms<T_Q6_K>(load_unit<T_Q6_K>(sg, lu.row, lu.u, g.U), rec, tm); break;
             }
         }
@@ -1622,6 +1705,18 @@ __device__ __forceinline__ float dequant_elem(const Seg& w, int row, int e, int 
     switch (w.type) {
         case T_F32: return ((const float*)w.a)[(size_t)row * cols + e];
         case T_F16: return h2f(((const uint16_t*)w.a)[(size_t)row * cols + e]);
+        case T_Q3_K: {  // A part c, dword m, byte i, field j = 2 hi + k; the inverted high bit above it (common.h)
+            const int t = e & 255, c = t >> 6, hi = (t >> 5) & 1, l = t & 7, i = (t & 31) >> 3, k = l >> 2, m = l & 3;
+            const int j = 2 * hi + k;
+            const int lo = (w.a[piece_off(row, c, u, U, 4, w.rgs) + 4 * m + i] >> (2 * j)) & 3;
+            const int hbit = ((8 * i + 2 * j + 2) & 31) + (c & 1);
+            const int hb = (w.h[piece_off(row, c >> 1, u, U, 2, w.rgs) + 4 * m + (hbit >> 3)] >> (hbit & 7)) & 1;
+            const uint32_t s0 = *(const uint32_t*)(w.s + ru * 12), s1 = *(const uint32_t*)(w.s + ru * 12 + 4),
+                           s2 = *(const uint32_t*)(w.s + ru * 12 + 8);
+            const int sc = q3_sc(q3_scales(s0, s1, s2)[c], t >> 4 & 3);
+            const float d = h2f(*(const uint16_t*)(w.d + ru * 2));
+            return d * (float)sc * (float)(lo - 4 * hb);
+        }
         case T_Q4_K:
         case T_Q5_K:
         case T_Q6_K: {

@@ -23,11 +23,14 @@ namespace llmi {
 #define LLMI_Q6_MASKED 1
 #endif
 constexpr bool kQ6Masked = LLMI_Q6_MASKED != 0;
+// the types whose dwords hold bytes of two sub-blocks and read the masked activation copies
+// (mv_device.h q6_masks_build): Q6_K and Q3_K, whose expansion lands in Q6_K's byte order
+__host__ __device__ constexpr bool mv_masked_type(int t) { return t == T_Q6_K || t == T_Q3_K; }
 // LDS of a k_matvec launch of NW waves whose pipelined types are T / T2
 __host__ inline size_t mv_lds_total(int act, int cols, int nw, int t, int t2, int x86 = 0) {
     const int ff = fold_stride_cols(act, x86, cols);
     const size_t base = fold_off(act, cols, nw) + (size_t)nw * ff * 4;
-    return base + ((kQ6Masked && !x86 && (t == T_Q6_K || t2 == T_Q6_K)) ? (size_t)(cols >> 8) * kQ6MaskRec : 0);
+    return base + ((kQ6Masked && !x86 && (mv_masked_type(t) || mv_masked_type(t2))) ? (size_t)(cols >> 8) * kQ6MaskRec : 0);
 }
 
 static int g_split_by_pairs = getenv("LLMI_SPLIT_BY_PAIRS") ? atoi(getenv("LLMI_SPLIT_BY_PAIRS")) : 0;  // A/B only
@@ -96,7 +99,7 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const MVL
     __syncthreads();
     // Q6_K: the masked activation copies (mv_device.h q6_masks_build), after the fold buffers
     [[maybe_unused]] uint8_t* q6m = nullptr;
-    if constexpr (T == T_Q6_K && kQ6Masked && !X86) {
+    if constexpr (mv_masked_type(T) && kQ6Masked && !X86) {
         q6m = (uint8_t*)L.act + fold_off(ACT, E.cols, NT / 64) + (size_t)(NT / 64) * kFoldFloats * 4;
         q6_masks_build<NT>(L, g.U, q6m);
         __syncthreads();
@@ -153,6 +156,8 @@ __device__ __forceinline__ unsigned long long mv_body(const MVArgs& A, const MVL
                 unit_store_x86<T>(cur, L.act + (size_t)lu.u * kRec, F, r, ul, g.lr, g.R, lu.valid);
             else if constexpr (T == T_Q6_K && kQ6Masked)
                 unit_terms_q6m(cur, q6m + (size_t)lu.u * kQ6MaskRec, *(const float*)(L.act + (size_t)lu.u * kRec + kRecD), tm);
+            else if constexpr (T == T_Q3_K && kQ6Masked)
+                q3_terms<true>(cur, q6m + (size_t)lu.u * kQ6MaskRec, *(const float*)(L.act + (size_t)lu.u * kRec + kRecD), tm);
             else
                 unit_terms<T>(cur, L.act + (size_t)lu.u * kRec, tm);
             sub_finish<ACT, EPI, MVArgs, X86>(A, F, g, s, b, sg, tm, lu, r, ul, acc, vg, pos, best);

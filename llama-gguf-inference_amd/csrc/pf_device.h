@@ -54,7 +54,7 @@ __device__ __forceinline__ RowPtr row_ptr(const Seg& s, int row, int cols) {
     r.ps = (U * 16u) << s.rgs;
     r.qa = s.a + piece_off((uint32_t)row, 0, 0, U, unit_parts<T>(), s.rgs);
     r.hb = s.h + piece_off((uint32_t)row, 0, 0, U, unit_hparts<T>(), s.rgs);
-    r.sb = s.s + ru * 16;
+    r.sb = s.s + ru * (T == T_Q3_K ? 12 : 16);
     r.db = s.d + ru * (T == T_Q8_0 ? 16 : 2);
     return r;
 }
@@ -87,6 +87,14 @@ __device__ __forceinline__ PfW<T> pf_w_load(const RowPtr& rp, int stage, int) {
         for (int l = 0; l < 8; ++l)
             w.q8[l] = *(const u32x2*)(rp.qa + (2 * l + (g >> 1)) * rp.ps + st * 16 + 8 * (g & 1));
         w.dd = *(const u32x4*)(rp.db + st * 16);
+    } else if constexpr (T == T_Q3_K) {
+        // chunk g: A part g; its inverted high bits in H part g / 2, shifted down for the odd
+        // chunk (common.h); q1 = the unit's 12 scale bytes
+        w.q0 = pf_ld16(rp.qa + g * rp.ps + st * 16);
+        const u32x4 h = pf_ld16(rp.hb + (g >> 1) * rp.ps + st * 16);
+        w.hdr = h >> (g & 1);
+        w.q1 = u32x4{pf_ld4(rp.sb + st * 12), pf_ld4(rp.sb + st * 12 + 4), pf_ld4(rp.sb + st * 12 + 8), 0u};
+        w.d = *(const uint16_t*)(rp.db + st * 2);
     } else {
         w.q0 = pf_ld16(rp.qa + (2 * g) * rp.ps + st * 16);
         w.q1 = pf_ld16(rp.qa + (2 * g + 1) * rp.ps + st * 16);
@@ -137,6 +145,26 @@ __device__ __forceinline__ void pf_build_b(const PfW<T>& w, int l, h2 slo, h2 sh
             const h2 x = as_h2(pf_magic(v[k])) - h2{(_Float16)1152.f, (_Float16)1152.f};
             r[2 * k] = x[0];
             r[2 * k + 1] = x[1];
+        }
+        out[0] = r;
+    } else if constexpr (T == T_Q3_K) {
+        // residue l = 4k + m: fields k (LO) and 2 + k (HI) of dword m, as q3_dword leaves them:
+        // bits 7..5 of a byte = q in 3-bit two's complement; q + 4 = those bits XOR 4, an exact
+        // f16 by the magic number, minus 1028, times the sub-block's scale: |scale q| <= 128,
+        // exact.  s6[k] = scale - 32 of sub-block 4g + k; pairs as Q6_K's: LO bytes 0,1 sub-block
+        // 4g, bytes 2,3 4g + 1, HI 4g + 2, 4g + 3
+        const int k = l >> 2, m = l & 3;
+        h8 r;
+#pragma unroll
+        for (int hi = 0; hi < 2; ++hi) {
+            const uint32_t y = (q3_dword(w.q0[m], w.hdr[m], 2 * hi + k) >> 5) ^ 0x04040404u;
+            const uint32_t x01 = __builtin_amdgcn_perm(0u, y, 0x0c010c00u), x23 = __builtin_amdgcn_perm(0u, y, 0x0c030c02u);
+            const h2 off = h2{(_Float16)1028.f, (_Float16)1028.f};
+            const h2 a = (as_h2(pf_magic(x01)) - off) * s6[2 * hi], b = (as_h2(pf_magic(x23)) - off) * s6[2 * hi + 1];
+            r[4 * hi] = a[0];
+            r[4 * hi + 1] = a[1];
+            r[4 * hi + 2] = b[0];
+            r[4 * hi + 3] = b[1];
         }
         out[0] = r;
     } else {

@@ -397,6 +397,14 @@ __global__ __launch_bounds__(256, T == T_Q8_0 ? 1 : 2) void k_pf_gemm(PfGemm g) 
                     bm[1] = (_Float16)(float)(64 * m0);
                     bm[2] = (_Float16)(float)m1;
                     bm[3] = (_Float16)(float)(64 * m1);
+                } else if constexpr (T == T_Q3_K) {  // scale - 32 of sub-blocks 4 grp + k: |scale q| <= 128, one fragment
+                    dw = h2f(wcur.d);
+                    const uint32_t s4 = q3_scales(wcur.q1.x, wcur.q1.y, wcur.q1.z)[grp];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const _Float16 fs = (_Float16)(float)q3_sc(s4, k);
+                        s6[k] = h2{fs, fs};
+                    }
                 } else {  // Q6_K: sc = 16 sh + sl per sub-block 4 grp + k
                     dw = h2f(wcur.d);
 #pragma unroll
@@ -470,7 +478,7 @@ __global__ __launch_bounds__(256, T == T_Q8_0 ? 1 : 2) void k_pf_gemm(PfGemm g) 
                             sumf[2 * tl + h] = fma2(dm, f2v{si[2 * h], si[2 * h + 1]}, sumf[2 * tl + h]);
                         }
                     }
-                } else if constexpr (T != T_Q6_K) {  // sumf -= (dmin * d_a) * sumi; sumi = mins . bsum pairs on the MFMA (exact)
+                } else if constexpr (T != T_Q6_K && T != T_Q3_K) {  // sumf -= (dmin * d_a) * sumi; sumi = mins . bsum pairs on the MFMA (exact)
 #pragma unroll
                     for (int tl = 0; tl < NTL; ++tl) {
                         const h8 af = *(const h8*)(Lbf + (tl >> 1) * 2048 + ((size_t)grp * 32 + 16 * (tl & 1) + (lane & 15)) * 16);
@@ -1203,11 +1211,15 @@ static hipError_t pf_gemm_launch(const PfGemm& g0, hipStream_t s) {
     const PfGemm& g = g0;
 #endif
     if (g.w.x86) {  // x86 numerics: 32-token workgroups (the 8-12 chains per row: register room)
-        const dim3 grid((g.rows + kPfRows - 1) / kPfRows, (g.T + 31) / 32);
-        PfGemm gx = g;
-        gx.xcd_map = pf_xcd_sy(grid);
-        launch_k(k_pf_gemm<T, EPI, 1, 1>, grid, dim3(256), 2 * PfBuf<1>::BYTES, s, true, true, gx);
-        return hipGetLastError();
+        if constexpr (T == T_Q3_K) {
+            return hipErrorNotSupported;  // Q3_K: generic numerics only
+        } else {
+            const dim3 grid((g.rows + kPfRows - 1) / kPfRows, (g.T + 31) / 32);
+            PfGemm gx = g;
+            gx.xcd_map = pf_xcd_sy(grid);
+            launch_k(k_pf_gemm<T, EPI, 1, 1>, grid, dim3(256), 2 * PfBuf<1>::BYTES, s, true, true, gx);
+            return hipGetLastError();
+        }
     }
     // 64 tokens per workgroup (NG = 2) while that still gives every CU a workgroup (at
     // fewer, 32-token workgroups: twice the grid); activation rows are padded to a
@@ -1238,11 +1250,12 @@ static hipError_t pf_gemm_epi(const PfGemm& g, int epi, hipStream_t s) {
 }
 bool pf_gemm_ok(int type, int rows, int cols) {
     if (rows % 16 || rows <= 0 || cols % 256 || cols <= 0) return false;
-    return type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0;
+    return type == T_Q3_K || type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0;
 }
 hipError_t launch_pf_gemm(const PfGemm& g, int epi, hipStream_t s) {
     if (!pf_gemm_ok(g.w.type, g.rows, g.cols) || g.T <= 0) return hipErrorInvalidValue;
     switch (g.w.type) {
+        case T_Q3_K: return pf_gemm_epi<T_Q3_K>(g, epi, s);
         case T_Q4_K: return pf_gemm_epi<T_Q4_K>(g, epi, s);
         case T_Q5_K: return pf_gemm_epi<T_Q5_K>(g, epi, s);
         case T_Q6_K: return pf_gemm_epi<T_Q6_K>(g, epi, s);

@@ -8,24 +8,30 @@ import numpy as np
 import torch
 from llmi._lib import lib
 from helpers import random_blocks, Q4_K, Q5_K, Q6_K, Q8_0
+from q3k_cases import Q3_K, random_q3k, twin_q6k
 L = lib()
 P = lambda t: C.c_void_p(t.data_ptr())
 res = {}
 shapes = [(Q4_K, 28672, 4096), (Q4_K, 4096, 14336), (Q6_K, 4096, 14336), (Q6_K, 128256, 4096), (Q4_K, 6144, 4096),
           (Q5_K, 14336, 4096), (Q8_0, 5632, 2048)]
-if os.environ.get("MV_SHAPES"):  # e.g. "12:28672x4096,14:128256x4096"
+if os.environ.get("MV_SHAPES"):  # e.g. "12:28672x4096,14:128256x4096"; 11 = Q3_K, 11t = the Q6_K twin of that matrix
     shapes = []
     for tok in os.environ["MV_SHAPES"].split(","):
         t, rc = tok.split(":"); r, c = rc.split("x")
-        shapes.append((int(t), int(r), int(c)))
+        shapes.append((t if t == "11t" else int(t), int(r), int(c)))
 REPS = int(os.environ.get("MV_REPS", "200"))
 MODE = int(os.environ.get("MV_MODE", "0"))  # bit0 fused RMSNorm, bit1 logits epilogue
 rng = np.random.default_rng(0)
 for qt, rows, cols in shapes:
+    key = f"{qt}:{rows}x{cols}"
+    # (11 and 11t: a seed of their own, so that both hold the same matrix)
+    blocks = random_q3k(rows, cols, np.random.default_rng(11)) if qt in (Q3_K, "11t") else random_blocks(qt, rows, cols, rng)
+    if qt == "11t":
+        qt, blocks = Q6_K, twin_q6k(blocks)
     lb = L.llmi_device_layout_bytes(qt, rows, cols)
     stride = (lb + 4095) // 4096 * 4096
     n = int(os.environ.get("MV_NCOPIES", "0")) or max(2, int(np.ceil(1.2e9 / stride)))
-    raw = torch.from_numpy(random_blocks(qt, rows, cols, rng)).cuda()
+    raw = torch.from_numpy(blocks).cuda()
     w = torch.empty(stride * n, dtype=torch.uint8, device="cuda")
     for k in range(n):
         assert L.llmi_repack(qt, P(raw), C.c_void_p(w.data_ptr() + stride * k), rows, cols) == 0
@@ -34,7 +40,6 @@ for qt, rows, cols in shapes:
     us = L.llmi_bench_matvec_ex(qt, P(w), n, rows, cols, P(x), P(y), REPS, MODE)
     alg = raw.numel()
     us_s = L.llmi_bench_stream(P(w), n, stride, alg, REPS, 2048)
-    key = f"{qt}:{rows}x{cols}"
     res[key] = {"us": us, "GBps": alg / us / 1e3, "stream_us": us_s, "stream_GBps": alg / us_s / 1e3}
     print(key, json.dumps(res[key]), flush=True)
     del w, raw
