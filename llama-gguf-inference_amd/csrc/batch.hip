@@ -19,7 +19,22 @@
 #include <mutex>
 #include <tuple>
 
+// batch_q3k.hip includes this file with LLMI_BATCH_Q3K = 1: the T_Q3_K instantiations of the
+// kernels below, behind mvn_q3k / bmm_q3k / bmm2_q3k, compile as a unit of their own
+#ifndef LLMI_BATCH_Q3K
+#define LLMI_BATCH_Q3K 0
+#endif
+// A/B: 1 = k_bmd<T_Q3_K> has one weight round buffer, as the other types (default); 2 = two,
+// the next round's DMA issued a barrier earlier (measured slower: profiles/q3k_batch/)
+#ifndef LLMI_BMD_Q3K_BUFS
+#define LLMI_BMD_Q3K_BUFS 1
+#endif
+
 namespace llmi {
+
+hipError_t mvn_q3k(const MVArgs& a, int epi, int nt, int max_blocks, hipStream_t s);
+hipError_t bmm_q3k(const MVArgs& a, int epi, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s);
+hipError_t bmm2_q3k(const MVArgs& a1, const MVArgs& a2, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s);
 
 namespace {
 
@@ -223,6 +238,7 @@ __global__ __launch_bounds__(kBT) void k_mvn(MVArgs A) {
 
 // batched step entry: per slot (blockIdx.y) the token (host-provided for this position,
 // else the argmax of the sequence's previous step), the sequence state, the embedding row
+#if !LLMI_BATCH_Q3K
 __global__ __launch_bounds__(256) void k_bembed(BEmbArgs a) {
     const int s = blockIdx.y;
     const int seq = a.tseq[s];
@@ -252,6 +268,7 @@ __global__ __launch_bounds__(256) void k_bembed(BEmbArgs a) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e < a.cols) a.x[(size_t)s * a.cols + e] = dequant_elem(a.w, tok, e, a.cols);
 }
+#endif
 
 // ---- the batched matvec on the matrix cores ---------------------------------------------
 // k_bmm: workgroup = one ROW TILE of 16 rows (SWIGLU: 16 gate rows and the same 16 up
@@ -267,11 +284,13 @@ __global__ __launch_bounds__(256) void k_bembed(BEmbArgs a) {
 // token's results equal its single-sequence decode (k_matvec) and the oracle bit for bit.
 // The padded token rows of the MFMA are zero fragments (bm_load zeroes them; discarded).
 constexpr int kBmW = 8, kBmT = kBmW * 64;
-// chains per (row, token): generic 8 residues + sumf (Q6_K: no mins); x86 (X86 = 1, model
+// chains per (row, token): generic 8 residues + sumf (Q6_K, Q3_K: no mins); x86 (X86 = 1, model
 // numerics LLMI_NUMERICS_X86) the 8 AVX2 lanes + Q4_K's 4 min lanes / Q5_K's summs.  A
 // round buffer holds bm_ns() term slots per (stage, matrix): generic 9, x86 one per chain.
+template <int T>
+__host__ __device__ constexpr bool bm_nomins() { return T == T_Q6_K || T == T_Q3_K; }
 template <int T, int X86>
-__host__ __device__ constexpr int bm_nc() { return X86 ? (T == T_Q4_K ? 12 : T == T_Q5_K ? 9 : 8) : (T == T_Q6_K ? 8 : 9); }
+__host__ __device__ constexpr int bm_nc() { return X86 ? (T == T_Q4_K ? 12 : T == T_Q5_K ? 9 : 8) : (bm_nomins<T>() ? 8 : 9); }
 template <int T, int X86>
 __host__ __device__ constexpr int bm_ns() { return X86 ? bm_nc<T, X86>() : 9; }
 
@@ -288,9 +307,20 @@ __device__ __forceinline__ void bm_load(BmStage<T, NW>& st, const RowPtr (&rp)[N
                                         const uint8_t* abf, const float* ad, int s, int S, int nt, int exp = 0,
                                         bool weights = true) {
     const int lane = threadIdx.x & 63, n = lane & 15, grp = lane >> 4;
-    if (weights)
+    if (weights) {
 #pragma unroll
         for (int wi = 0; wi < NW; ++wi) st.w[wi] = pf_w_load<T>(rp[wi], s, S);
+    } else if constexpr (T == T_Q3_K) {
+        // k_bmd: the stage's 12 scale bytes (rows at a 12 U stride: no 16-B DMA piece is
+        // aligned) and d stay global loads, issued here a stage ahead with the activations;
+        // bmd_w adds the quant parts from the round buffer
+#pragma unroll
+        for (int wi = 0; wi < NW; ++wi) {
+            const uint8_t* sp = rp[wi].sb + (uint32_t)s * 12;
+            st.w[wi].q1 = u32x4{pf_ld4(sp), pf_ld4(sp + 4), pf_ld4(sp + 8), 0u};
+            st.w[wi].d = *(const uint16_t*)(rp[wi].db + (uint32_t)s * 2);
+        }
+    }
     // only the lanes of real tokens load (the padding rows' loads would repeat token 0's
     // fragments through the TA); the others keep zeros
     int ntl = nt;
@@ -310,7 +340,7 @@ __device__ __forceinline__ void bm_load(BmStage<T, NW>& st, const RowPtr (&rp)[N
             st.da[i] = ad[(size_t)t * S + s];
         }
     }
-    if constexpr (T != T_Q6_K) st.bs = n < ntl ? *(const h8*)(abf + pf_abf_off(n, s, grp, S)) : h8{};
+    if constexpr (!bm_nomins<T>()) st.bs = n < ntl ? *(const h8*)(abf + pf_abf_off(n, s, grp, S)) : h8{};
 }
 
 // the stage's terms tm[wi][chain][i] (token 4 grp + i, row lane & 15).  X86: the chains'
@@ -342,6 +372,16 @@ __device__ __forceinline__ void bm_terms(const BmStage<T, NW>& st, float (&tm)[N
             bm[1] = (_Float16)(float)(64 * m0);
             bm[2] = (_Float16)(float)m1;
             bm[3] = (_Float16)(float)(64 * m1);
+        } else if constexpr (T == T_Q3_K) {
+            // scale - 32 of sub-blocks 4 grp + k (the kmask unpack): |scale q| <= 128, so one
+            // fragment and one MFMA per residue, no recombination, no mins
+            dw = h2f(w.d);
+            const uint32_t s4 = q3_scales(w.q1.x, w.q1.y, w.q1.z)[grp];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const _Float16 fs = (_Float16)(float)q3_sc(s4, k);
+                s6[k] = h2{fs, fs};
+            }
         } else {  // Q6_K: sc = 16 sh + sl per sub-block 4 grp + k
             dw = h2f(w.d);
 #pragma unroll
@@ -391,9 +431,9 @@ __device__ __forceinline__ void bm_terms(const BmStage<T, NW>& st, float (&tm)[N
             // sumi = mins . bsum pairs on the MFMA (every product and partial sum an integer
             // < 2^24: exact, prefill.hip k_pf_quant); the term -(dmin * d_a) * sumi
             f4 sm{0.f, 0.f, 0.f, 0.f};
-            if constexpr (T != T_Q6_K) sm = mfma16(st.bs, bm, f4{0.f, 0.f, 0.f, 0.f});
+            if constexpr (!bm_nomins<T>()) sm = mfma16(st.bs, bm, f4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
-            for (int i = 0; i < 4; ++i) tm[wi][8][i] = T != T_Q6_K ? -(dm[i] * sm[i]) : 0.f;
+            for (int i = 0; i < 4; ++i) tm[wi][8][i] = !bm_nomins<T>() ? -(dm[i] * sm[i]) : 0.f;
         }
     }
 }
@@ -494,7 +534,7 @@ __global__ __launch_bounds__(kBmT) void k_bmm(MVArgs A, const uint8_t* aq, const
                                               int ntiles) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NW = EPI == EPI_SWIGLU ? 2 : 1;   // weight matrices (SWIGLU: gate, up)
-    constexpr int NC = T == T_Q6_K ? 8 : 9;         // chains per (row, token)
+    constexpr int NC = bm_nc<T, 0>();               // chains per (row, token)
     constexpr int kBuf = kBmW * NW * 9 * 32;        // float4 per round buffer
     float4* TmB = (float4*)smem;
     float4* G = TmB + 2 * kBuf;
@@ -601,15 +641,35 @@ __global__ __launch_bounds__(kBmT) void k_bmm(MVArgs A, const uint8_t* aq, const
 // same fold: bit-identical to k_bmm.
 typedef __attribute__((address_space(3))) void* bmd_lds_vp;
 typedef __attribute__((address_space(1))) void* bmd_glb_vp;
+//
+// Q3_K has a round layout of its own: 6 segments per (matrix, row) -- the 4 A parts and the 2
+// H parts, 768 B per row and round against Q6_K's 1664.  Its scale plane is 12 B per unit, so
+// a row's scales start 16-B aligned only where U % 4 == 0 and no 16-B DMA piece fits it:
+// the three scale dwords (and d) of a stage are plain global loads, issued one stage ahead
+// with the activations (bm_load).  LDS: 36864 terms + 4608 G + 12288 = 53760 B, SWIGLU 73728 +
+// 9216 + 24576 = 107520 B (Q6_K: 68096 / 136192 B).  The freed LDS holds a second round buffer
+// under LLMI_BMD_Q3K_BUFS=2 (bmd_nbuf; + 12288 / 24576 B): the DMA of round r + 1 then goes out
+// at the top of round r into the buffer round r - 1 was read from, ahead of the barrier that
+// releases round r's.  On the 8B Q3_K_M bench at 8 sequences that form ran 2040 tok/s against
+// 2155 with one buffer, so one buffer is the default.  A row's 768 B are a multiple of the 256 B of
+// bank space, so beside the slot swizzle rows 8..15 swap each segment pair (seg ^ 1): the 16
+// rows of a read land on the 16 different 16-B columns, any 8 consecutive on 8 of one half.
 template <int T>
-__host__ __device__ constexpr int bmd_nseg() { return T == T_Q4_K ? 9 : T == T_Q5_K ? 11 : 13; }
+__host__ __device__ constexpr int bmd_nseg() { return T == T_Q3_K ? 6 : T == T_Q4_K ? 9 : T == T_Q5_K ? 11 : 13; }
+template <int T>
+__host__ __device__ constexpr int bmd_nbuf() { return T == T_Q3_K ? LLMI_BMD_Q3K_BUFS : 1; }
 // bytes of a round's weight buffer
 template <int T, int NW>
 __host__ __device__ constexpr size_t bmd_wbytes() { return (size_t)NW * 16 * bmd_nseg<T>() * kBmW * 16; }
+// the segment whose pieces sit at position `seg` of row `row` of the round buffer
+template <int T>
+__device__ __forceinline__ int bmd_seg_at(int seg, int row) { return T == T_Q3_K ? seg ^ ((row >> 3) & 1) : seg; }
 // plane base of segment `seg` of a row (unit u at + 16 u): A parts 0..7, then Q4_K the
-// header; Q5_K the header and the two fifth-bit parts; Q6_K the four high-bit parts and the scales
+// header; Q5_K the header and the two fifth-bit parts; Q6_K the four high-bit parts and the
+// scales.  Q3_K: A parts 0..3, H parts 0, 1
 template <int T>
 __device__ __forceinline__ const uint8_t* bmd_seg_base(const RowPtr& rp, int seg) {
+    if constexpr (T == T_Q3_K) return seg < 4 ? rp.qa + (uint32_t)seg * rp.ps : rp.hb + (uint32_t)(seg - 4) * rp.ps;
     if (seg < 8) return rp.qa + (uint32_t)seg * rp.ps;
     if constexpr (T == T_Q4_K) return rp.sb;
     else if constexpr (T == T_Q5_K) return seg == 8 ? rp.sb : rp.hb + (uint32_t)(seg - 9) * rp.ps;
@@ -626,7 +686,7 @@ __device__ __forceinline__ void bmd_dma(const MVArgs& A, int si, int row0, int r
         const int seg = q % NSEG, rr = q / NSEG, row = rr % 16, mat = rr / 16;
         const int u = min(rho * kBmW + (slot ^ (row & 7)), U - 1);
         const RowPtr rp = row_ptr<T>(pick(A, EPI == EPI_SWIGLU ? mat : si), row0 + row, A.cols);
-        __builtin_amdgcn_global_load_lds((bmd_glb_vp)(bmd_seg_base<T>(rp, seg) + (uint32_t)u * 16),
+        __builtin_amdgcn_global_load_lds((bmd_glb_vp)(bmd_seg_base<T>(rp, bmd_seg_at<T>(seg, row)) + (uint32_t)u * 16),
                                          (bmd_lds_vp)(wb + (size_t)i * 1024), 16, 0, 0);
     }
 }
@@ -639,8 +699,17 @@ __device__ __forceinline__ void bmd_w(BmStage<T, NW>& st, const uint8_t* wb, int
     const int slot = stg ^ (row & 7);
 #pragma unroll
     for (int wi = 0; wi < NW; ++wi) {
-        auto piece = [&](int seg) { return wb + ((((size_t)(wi * 16 + row) * NSEG + seg) * kBmW + slot) * 16); };
+        auto piece = [&](int seg) {
+            return wb + ((((size_t)(wi * 16 + row) * NSEG + bmd_seg_at<T>(seg, row)) * kBmW + slot) * 16);
+        };
         PfW<T>& w = st.w[wi];
+        if constexpr (T == T_Q3_K) {
+            // pf_w_load<T_Q3_K>'s view: chunk g = A part g, its high bits in H part g / 2,
+            // shifted down for the odd chunk; q1 (the scale bytes) and d came with bm_load
+            w.q0 = *(const u32x4*)piece(g);
+            w.hdr = *(const u32x4*)piece(4 + (g >> 1)) >> (uint32_t)(g & 1);
+            continue;
+        }
         w.q0 = *(const u32x4*)piece(2 * g);
         w.q1 = *(const u32x4*)piece(2 * g + 1);
         if constexpr (T == T_Q4_K || T == T_Q5_K) {
@@ -659,7 +728,7 @@ __device__ __forceinline__ void bmd_w(BmStage<T, NW>& st, const uint8_t* wb, int
 template <int T, int NW, int X86>
 __host__ __device__ constexpr size_t bmd_lds() {
     return ((size_t)kBmW * NW * bm_ns<T, X86>() + (size_t)NW * bm_ns<T, X86>()) * 32 * 16 +
-           (X86 ? (size_t)kBmW * NW * 16 * 8 + (size_t)kBmW * 8 * 4 : 0) + bmd_wbytes<T, NW>();
+           (X86 ? (size_t)kBmW * NW * 16 * 8 + (size_t)kBmW * 8 * 4 : 0) + bmd_nbuf<T>() * bmd_wbytes<T, NW>();
 }
 
 // the persistent tile loop of one k_bmd workgroup: tiles tile0, tile0 + stride, ... < ntiles.
@@ -694,10 +763,13 @@ __device__ __forceinline__ void bmd_body(const MVArgs& A, const uint8_t* aq, con
     // explicit: a workgroup barrier alone need not wait for this wave's LDS-DMA writes
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // round 0 in LDS
+    // NB = 2 (Q3_K): round buffers Wb (this round) and Wn (the next) swap every iteration
+    constexpr int NB = bmd_nbuf<T>();
+    uint8_t* Wn = Wb + (NB - 1) * bmd_wbytes<T, NW>();
     int rho = 0;
     for (;;) {
         const int s = rho * kBmW + wave;
-        bmd_w<T, NW>(cur, Wb, wave, rp, s < S ? s : S - 1);
+        if constexpr (NB == 1) bmd_w<T, NW>(cur, Wb, wave, rp, s < S ? s : S - 1);
         int tn = tile, rn = rho + 1;
         if (rn == R) {
             rn = 0;
@@ -707,8 +779,14 @@ __device__ __forceinline__ void bmd_body(const MVArgs& A, const uint8_t* aq, con
         int sin, row0n;
         RowPtr rpn[NW];
         bm_tile<T, EPI, NW>(A, has_next ? tn : tile, sin, row0n, rpn);
-        __syncthreads();  // every wave has its stage out of the round buffer
-        if (has_next) bmd_dma<T, EPI, NW>(A, sin, row0n, rn, Wb);
+        if constexpr (NB == 2) {
+            // Wn was last read before the first barrier of the previous iteration: free now
+            if (has_next) bmd_dma<T, EPI, NW>(A, sin, row0n, rn, Wn);
+            bmd_w<T, NW>(cur, Wb, wave, rp, s < S ? s : S - 1);
+        }
+        __syncthreads();  // every wave has its stage out of the round buffer (NB = 2: the last fold is done with Tm)
+        if constexpr (NB == 1)
+            if (has_next) bmd_dma<T, EPI, NW>(A, sin, row0n, rn, Wb);
         const int sn = rn * kBmW + wave;
         BmStage<T, NW> nxt;
         bm_load<T, NW>(nxt, rpn, aq, abf, ad, sn < S ? sn : S - 1, S, nt, 0, false);
@@ -773,6 +851,11 @@ __device__ __forceinline__ void bmd_body(const MVArgs& A, const uint8_t* aq, con
             if (threadIdx.x < 64) bm_epilogue<T, EPI, NW, NC, X86>(A, G, nt, tile, si, row0);
         }
         if (!has_next) break;
+        if constexpr (NB == 2) {
+            uint8_t* const w = Wb;
+            Wb = Wn;
+            Wn = w;
+        }
         cur = nxt;
         tile = tn;
         rho = rn;
@@ -800,12 +883,14 @@ __global__ __launch_bounds__(kBmT) void k_bmd2(MVArgs A1, MVArgs A2, const uint8
 }
 
 // ---- launchers -----------------------------------------------------------------------------
+#if !LLMI_BATCH_Q3K
 size_t mvn_lds_bytes(int act, int cols, int nt, int x86) {
     const size_t fold = x86 ? (act ? (size_t)kX86QFloats : (size_t)kX86KFloats) : (size_t)kFoldFloats;
     (void)fold;
     return a16((size_t)nt * img_bytes(act, cols) + (size_t)kMaxBatch * kBW * 8) +
            (size_t)mvn_work_waves(act, x86) * fold_stride_cols(act, x86, cols) * 4;
 }
+#endif
 
 template <typename K>
 static int mvn_grid(K kernel, int ntasks, size_t lds, int max_blocks, int nwk) {
@@ -868,6 +953,11 @@ static hipError_t mvn_epi(const MVArgs& a, int epi, int nt, int mb, hipStream_t 
     }
 }
 
+#if LLMI_BATCH_Q3K
+hipError_t mvn_q3k(const MVArgs& a, int epi, int nt, int max_blocks, hipStream_t s) {
+    return mvn_epi<0, T_Q3_K, 0>(a, epi, nt, max_blocks, s);
+}
+#else
 static hipError_t mvn_type(const MVArgs& a, int epi, int nt, int max_blocks, hipStream_t s) {
     if (a.num) {  // x86 association
         switch (a.seg[0].type) {
@@ -883,6 +973,7 @@ static hipError_t mvn_type(const MVArgs& a, int epi, int nt, int max_blocks, hip
         case T_Q5_K: return mvn_epi<0, T_Q5_K, 0>(a, epi, nt, max_blocks, s);
         case T_Q6_K: return mvn_epi<0, T_Q6_K, 0>(a, epi, nt, max_blocks, s);
         case T_Q8_0: return mvn_epi<1, T_Q8_0, 0>(a, epi, nt, max_blocks, s);
+        case T_Q3_K: return mvn_q3k(a, epi, nt, max_blocks, s);  // generic numerics only
         default: return hipErrorInvalidValue;
     }
 }
@@ -930,6 +1021,7 @@ int bmm_min_tokens() {
     const char* e = getenv("LLMI_BMM_MIN");  // read per call (step capture): tests switch it
     return e ? atoi(e) : 3;
 }
+#endif
 
 // LLMI_BMM_DMA (A/B): 1 k_bmd (weights through LDS by DMA, default), 0 k_bmm; read per
 // launch (step capture), so tests can run both
@@ -938,13 +1030,14 @@ static int bmm_dma() {
     return e ? atoi(e) : 1;
 }
 
+#if !LLMI_BATCH_Q3K
 bool bmm_ok(const MVArgs& a, int epi) {
     if (!g_bmm_env || a.nseg < 1 || a.cols <= 0 || a.cols % 256) return false;
     if (a.num && !bmm_dma()) return false;  // the x86 fold is k_bmd's only
     for (int i = 0; i < a.nseg; ++i)
         if ((a.seg[i].x86 != 0) != (a.num != 0)) return false;  // the planes' byte order
     const int t = a.seg[0].type;
-    if (!(t == T_Q4_K || t == T_Q5_K || t == T_Q6_K)) return false;
+    if (!(t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || (t == T_Q3_K && !a.num))) return false;  // Q3_K: generic numerics only
     if (epi == EPI_SWIGLU && (a.nseg != 2 || a.seg[0].rows != a.seg[1].rows)) return false;
     for (int i = 0; i < a.nseg; ++i) {
         if (a.seg[i].type != t || a.seg[i].rows % 16) return false;
@@ -952,6 +1045,7 @@ bool bmm_ok(const MVArgs& a, int epi) {
     }
     return epi == EPI_STORE || epi == EPI_ADD || epi == EPI_QKV || epi == EPI_SWIGLU || epi == EPI_LOGITS;
 }
+#endif
 
 // Resident k_bmm workgroups on the CURRENT device, per (kernel, LDS bytes, device), with
 // the dynamic-LDS attribute set once per device: in-process replicas run one scheduler
@@ -1022,6 +1116,14 @@ static hipError_t bmm2_launch(const MVArgs& a1, const MVArgs& a2, const void* aq
     hipLaunchKernelGGL(k, dim3(w1 + w2), dim3(kBmT), lds, s, a1, a2, (const uint8_t*)aq, (const uint8_t*)abf, ad, nt, nt1, nt2, w1);
     return hipGetLastError();
 }
+#if LLMI_BATCH_Q3K
+// the Q3_K_M QKV: q / k in Q3_K, attn_v in Q4_K or Q5_K
+hipError_t bmm2_q3k(const MVArgs& a1, const MVArgs& a2, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s) {
+    if (a2.seg[0].type == T_Q4_K) return bmm2_launch<T_Q3_K, T_Q4_K, 0>(a1, a2, aq, abf, ad, nt, s);
+    if (a2.seg[0].type == T_Q5_K) return bmm2_launch<T_Q3_K, T_Q5_K, 0>(a1, a2, aq, abf, ad, nt, s);
+    return hipErrorNotSupported;
+}
+#else
 // LLMI_BMM2 (A/B): 1 mixed-type QKV in one k_bmd2 launch (default), 0 two launches
 static int bmm2_on() {
     const char* e = getenv("LLMI_BMM2");
@@ -1043,8 +1145,10 @@ hipError_t launch_bmm_qkv2(const MVArgs& a1, const MVArgs& a2, int nt, const voi
     if (t1 == T_Q4_K && t2 == T_Q6_K) return bmm2_launch<T_Q4_K, T_Q6_K, 0>(a1, a2, aq, abf, ad, nt, s);
     if (t1 == T_Q4_K && t2 == T_Q5_K) return bmm2_launch<T_Q4_K, T_Q5_K, 0>(a1, a2, aq, abf, ad, nt, s);
     if (t1 == T_Q5_K && t2 == T_Q6_K) return bmm2_launch<T_Q5_K, T_Q6_K, 0>(a1, a2, aq, abf, ad, nt, s);
+    if (t1 == T_Q3_K) return bmm2_q3k(a1, a2, aq, abf, ad, nt, s);
     return hipErrorNotSupported;
 }
+#endif
 
 template <int T, int X86>
 static hipError_t bmm_epi(const MVArgs& a, int epi, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s) {
@@ -1058,6 +1162,11 @@ static hipError_t bmm_epi(const MVArgs& a, int epi, const void* aq, const void* 
     }
 }
 
+#if LLMI_BATCH_Q3K
+hipError_t bmm_q3k(const MVArgs& a, int epi, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s) {
+    return bmm_epi<T_Q3_K, 0>(a, epi, aq, abf, ad, nt, s);
+}
+#else
 hipError_t launch_bmm(const MVArgs& a, int epi, int nt, const void* aq, const void* abf, const float* ad, hipStream_t s) {
     if (nt < 1 || nt > kMaxBatch || !bmm_ok(a, epi)) return hipErrorInvalidValue;
     if (a.num) {
@@ -1072,6 +1181,7 @@ hipError_t launch_bmm(const MVArgs& a, int epi, int nt, const void* aq, const vo
         case T_Q4_K: return bmm_epi<T_Q4_K, 0>(a, epi, aq, abf, ad, nt, s);
         case T_Q5_K: return bmm_epi<T_Q5_K, 0>(a, epi, aq, abf, ad, nt, s);
         case T_Q6_K: return bmm_epi<T_Q6_K, 0>(a, epi, aq, abf, ad, nt, s);
+        case T_Q3_K: return bmm_q3k(a, epi, aq, abf, ad, nt, s);
         default: return hipErrorInvalidValue;
     }
 }
@@ -1081,5 +1191,6 @@ hipError_t launch_bembed(const BEmbArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_bembed, dim3((a.cols + 255) / 256, a.nt), dim3(256), 0, s, a);
     return hipGetLastError();
 }
+#endif
 
 }  // namespace llmi

@@ -349,7 +349,8 @@ static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std
 
 // the batched step in this model's numerics: every numerics and weight type (generic and
 // x86 K-quant rows on the matrix cores from 3 tokens, the rest through k_mvn; x86 Q8_0
-// rows with 4 working waves per workgroup, batch.hip mvn_work_waves).  A layer whose
+// rows with 4 working waves per workgroup, batch.hip mvn_work_waves; Q3_K rows, generic
+// numerics only, through the same kernels: batch_q3k.hip).  A layer whose
 // ffn_gate and ffn_up differ in type has no batched step in any numerics (bstep_run's
 // error; llama_decode then steps such sequences one at a time)
 bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, int tail) {
@@ -357,12 +358,6 @@ bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& er
     if (nt < 1 || nt > kMaxBatch || c.n_seq < 2) { err = "batched step: 1..8 slots of a context with n_seq_max >= 2"; return false; }
     for (const Layer& L : c.m->layers)
         if (L.wg.type != L.wu.type) { err = "batched step: ffn_gate / ffn_up of different types"; return false; }
-    // Q3_K has no batched kernels (k_mvn / k_bmd / k_bmm): such a model steps its sequences one at a time
-    auto q3 = [](const DevMat& d) { return d.type == T_Q3_K; };
-    bool has_q3 = q3(c.m->tok_embd) || q3(c.m->output);
-    for (const Layer& L : c.m->layers)
-        has_q3 = has_q3 || q3(L.wq) || q3(L.wk) || q3(L.wv) || q3(L.wo) || q3(L.wg) || q3(L.wu) || q3(L.wd);
-    if (has_q3) { err = "batched step: no batched kernels for q3_K weights"; return false; }
     if (!balloc(c, err)) return false;
     const int bucket = max_pos / 256;
     const int kv_bound = kv_bucket_bound(max_pos + 1, c.n_ctx);
