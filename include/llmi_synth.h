@@ -14,6 +14,7 @@
  *   Q6_K 210 B {u8 ql[128], u8 qh[64], i8 scales[16], f16 d}
  *   Q8_0  34 B {f16 d, i8 qs[32]}
  *   Q3_K 110 B {u8 hmask[32], u8 qs[64], u8 scales[12], f16 d}
+ *   Q2_K  84 B {u8 scales[16], u8 qs[64], f16 d, f16 dmin}
  */
 #ifndef LLMI_SYNTH_H
 #define LLMI_SYNTH_H
@@ -21,7 +22,7 @@
 #include "llmi_math.h"
 
 enum {
-    LLMI_T_F32 = 0, LLMI_T_F16 = 1, LLMI_T_Q8_0 = 8, LLMI_T_Q3_K = 11, LLMI_T_Q4_K = 12,
+    LLMI_T_F32 = 0, LLMI_T_F16 = 1, LLMI_T_Q8_0 = 8, LLMI_T_Q2_K = 10, LLMI_T_Q3_K = 11, LLMI_T_Q4_K = 12,
     LLMI_T_Q5_K = 13, LLMI_T_Q6_K = 14, LLMI_T_Q8_K = 15
 };
 
@@ -31,6 +32,10 @@ enum {
 #define LLMI_SYN_D_Q6K 2.93e-5f  /* std(d*sc*(q-32)) = 682.9*d */
 #define LLMI_SYN_D_Q80 2.73e-4f  /* std(d*q), q uniform in [-127,127] = 73.3*d */
 #define LLMI_SYN_D_Q3K 4.61e-4f  /* std(d*(sc-32)*q), sc in [0,63], q in [-4,3] = 43.3*d */
+/* Q2_K: w = d*sc*q - dmin*m with sc, m uniform in [0,15], q in [0,3], independent.  mean = 11.25*d
+ * - 7.5*dmin = 0 gives dmin = 1.5*d; var(sc*q) = 77.5*3.5 - 11.25^2 = 144.69, var(1.5*m) =
+ * 2.25*21.25 = 47.81, so std = sqrt(192.5)*d = 13.87*d */
+#define LLMI_SYN_D_Q2K 1.44e-3f  /* std(d*sc*q - 1.5*d*m) = 13.87*d */
 
 /* Writes one quantized block of `type` (block index `bi` inside tensor `tensor`). */
 LLMI_HD void llmi_synth_block(int type, uint64_t seed, uint64_t tensor, uint64_t bi, uint8_t* out) {
@@ -55,6 +60,12 @@ LLMI_HD void llmi_synth_block(int type, uint64_t seed, uint64_t tensor, uint64_t
         for (int k = 0; k < 108; ++k) out[k] = LLMI_SB(k);              /* hmask, qs, scales */
         uint16_t hd = llmi_f2h(LLMI_SYN_D_Q3K * jit);
         out[108] = (uint8_t)hd; out[109] = (uint8_t)(hd >> 8);
+    } else if (type == LLMI_T_Q2_K) {
+        for (int k = 0; k < 80; ++k) out[k] = LLMI_SB(k);               /* scales, qs */
+        float d = LLMI_SYN_D_Q2K * jit;
+        uint16_t hd = llmi_f2h(d), hm = llmi_f2h(d * 1.5f);
+        out[80] = (uint8_t)hd; out[81] = (uint8_t)(hd >> 8);
+        out[82] = (uint8_t)hm; out[83] = (uint8_t)(hm >> 8);
     } else if (type == LLMI_T_Q8_0) {
         uint16_t hd = llmi_f2h(LLMI_SYN_D_Q80 * jit);
         out[0] = (uint8_t)hd; out[1] = (uint8_t)(hd >> 8);

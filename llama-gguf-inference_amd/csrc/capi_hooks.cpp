@@ -397,6 +397,10 @@ int32_t llmi_bmv(int32_t type, const void* w, int64_t rows, int64_t cols, const 
     a.nw = nw; a.eps = eps;
     a.x_stride = (int)cols; a.y_stride = (int)rows;
     a.num = t_hook_numerics & NUMERICS_X86;
+    if (type == T_Q2_K) {  // neither k_mvn nor the matrix-core kernels are instantiated for it
+        set_err("llmi_bmv: no batched kernels for q2_K weights");
+        return -1;
+    }
     // never a silent fall-back to k_mvn (host check, before any device call)
     if (kernel == 1 && !bmm_ok(a, EPI_STORE)) {
         set_err("llmi_bmv: the matrix-core kernels do not take these arguments (type, rows % 16, numerics, LLMI_BMM*)");

@@ -17,6 +17,8 @@
 //   Q8_0  A: qs 256 B/unit (part p = 32-block p/2, half p%2)   D: 8 fp16 d = 16 B/unit
 //   Q3_K  A: 2-bit lows 64 B/unit: [row][4][unit][16 B]   H: [row][2][unit][16 B] high bits
 //         (inverted)   S: the 12 packed 6-bit scale bytes per unit   D: fp16 d 2 B/unit
+//   Q2_K  A: 2-bit quants 64 B/unit: [row][4][unit][16 B]   S: the 16 scale/min bytes per unit
+//         (bytes 1 and 2 of each dword swapped)   D: {fp16 d, fp16 dmin} 4 B/unit
 //   F32/F16 plain (A).
 // K-quant parts are in RESIDUE ORDER: part p = 2c + k of chunk c (64 weights: low
 // nibbles = weights 64c + t, high nibbles = 64c + 32 + t of native qs[32c + t]), byte
@@ -35,6 +37,15 @@
 // directly above its 2-bit field (field 3 of byte 3 wraps to bit 0), odd chunks one bit up.  So
 // (a & field mask) | ((h >> (c & 1)) & bit mask), rotated to the top of each byte, is four
 // signed bytes 32 q: three VALU per dword, no per-byte subtract (mv_device.h q3_dword).
+// Q2_K (generic numerics only) has Q3_K's A plane: chunk c is A part c, and field j = 2 hi + k
+// of byte i of dword m is the quant of chunk element 32 hi + 4k + m + 8i, so (a >> 2j) & 0x03030303
+// meets dword m of part 2c + k (LO for hi = 0, HI for hi = 1) of the activation image whole.
+// Bytes 0, 1 of such a dword are of sub-block 4c + 2 hi, bytes 2, 3 of sub-block 4c + 2 hi + 1:
+// the S plane keeps native scales[4w .. 4w + 3] in dword w as bytes {4w, 4w + 2, 4w + 1, 4w + 3},
+// so (S[w] >> 8 t) & 0x000F000F is the scale pair of sub-blocks 4w + 2t, 4w + 2t + 1 in the
+// two 16-bit halves and (S[w] >> (8 t + 4)) & 0x000F000F their mins: one packed 16-bit multiply
+// turns a field dword into four bytes scale * q <= 45 (mv_device.h q2_term), and the min pairs
+// meet the activation record's int16 bsum pairs in v_dot2.
 #pragma once
 
 #include <cstddef>
@@ -46,14 +57,15 @@ namespace llmi {
 
 enum : int {
     T_F32 = LLMI_T_F32, T_F16 = LLMI_T_F16, T_Q8_0 = LLMI_T_Q8_0,
-    T_Q4_K = LLMI_T_Q4_K, T_Q5_K = LLMI_T_Q5_K, T_Q6_K = LLMI_T_Q6_K, T_Q3_K = LLMI_T_Q3_K
+    T_Q4_K = LLMI_T_Q4_K, T_Q5_K = LLMI_T_Q5_K, T_Q6_K = LLMI_T_Q6_K, T_Q3_K = LLMI_T_Q3_K,
+    T_Q2_K = LLMI_T_Q2_K
 };
 
 inline int block_elems(int t) {
     switch (t) {
         case T_F32: case T_F16: return 1;
         case T_Q8_0: return 32;
-        case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: return 256;
+        case T_Q2_K: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: return 256;
         default: return 0;
     }
 }
@@ -61,17 +73,17 @@ inline int block_bytes(int t) {
     switch (t) {
         case T_F32: return 4; case T_F16: return 2; case T_Q8_0: return 34;
         case T_Q4_K: return 144; case T_Q5_K: return 176; case T_Q6_K: return 210;
-        case T_Q3_K: return 110;
+        case T_Q3_K: return 110; case T_Q2_K: return 84;
         default: return 0;
     }
 }
-inline bool is_kquant(int t) { return t == T_Q3_K || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K; }
+inline bool is_kquant(int t) { return t == T_Q2_K || t == T_Q3_K || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K; }
 inline bool type_supported(int t) { return block_bytes(t) != 0; }
 inline const char* type_name(int t) {
     switch (t) {
         case T_F32: return "f32"; case T_F16: return "f16"; case T_Q8_0: return "q8_0";
         case T_Q4_K: return "q4_K"; case T_Q5_K: return "q5_K"; case T_Q6_K: return "q6_K";
-        case T_Q3_K: return "q3_K";
+        case T_Q3_K: return "q3_K"; case T_Q2_K: return "q2_K";
         default: return "?";
     }
 }
@@ -135,6 +147,10 @@ inline size_t plan_planes(DevMat& m, size_t base) {
             m.off_s = align_up(m.off_h + nblk * 32, 256);
             m.off_d = align_up(m.off_s + nblk * 12, 256);
             return m.off_d + nblk * 2;
+        case T_Q2_K:
+            m.off_s = align_up(m.off_a + nblk * 64, 256);
+            m.off_d = align_up(m.off_s + nblk * 16, 256);
+            return m.off_d + nblk * 4;
         case T_Q8_0:
             m.off_d = align_up(m.off_a + nblk * 32, 256);
             return m.off_d + nblk * 2;
@@ -144,13 +160,13 @@ inline size_t plan_planes(DevMat& m, size_t base) {
 }
 inline bool needs_repack(int t) { return is_kquant(t) || t == T_Q8_0; }
 // piece_off (mv_device.h) and the kernels' plane offsets are 32-bit: the largest plane of a
-// repacked matrix, A (128 B per K-quant block, 64 B per Q3_K block, 32 B per Q8_0 block), must
+// repacked matrix, A (128 B per K-quant block, 64 B per Q3_K or Q2_K block, 32 B per Q8_0 block), must
 // end below 4 GiB.
 // rows, cols > 0.
 constexpr const char* kPlaneLimitMsg = "the matrix's quant plane reaches 4 GiB (32-bit piece offsets)";
 inline bool planes_fit_u32(int t, int64_t rows, int64_t cols) {
     if (!needs_repack(t)) return true;
-    const int64_t per_row = cols / block_elems(t) * (t == T_Q8_0 ? 32 : t == T_Q3_K ? 64 : 128);
+    const int64_t per_row = cols / block_elems(t) * (t == T_Q8_0 ? 32 : (t == T_Q3_K || t == T_Q2_K) ? 64 : 128);
     return per_row < ((int64_t)1 << 32) && rows <= (((int64_t)1 << 32) - 1) / (per_row > 0 ? per_row : 1);
 }
 

@@ -82,6 +82,13 @@ int main() {
         CHECK(llmi::plan_planes(m, 0) == 1536 + 12 * 2 && m.off_h == 768 && m.off_s == 768 + 512 && m.off_d == 1024 + 512);
         CHECK(m.bytes == 12 * 110 && m.rgs == 1);
     }
+    CHECK(!planes_fit_u32(llmi::T_Q2_K, 1 << 26, 256) && planes_fit_u32(llmi::T_Q2_K, (1 << 26) - 1, 256));
+    {  // Q2_K's planes: 64 + 16 + 4 B per unit, each plane 256-B aligned, GGUF's byte count
+        llmi::DevMat m;
+        m.type = llmi::T_Q2_K; m.rows = 6; m.cols = 512;
+        CHECK(llmi::plan_planes(m, 0) == 1024 + 12 * 4 && m.off_s == 768 && m.off_d == 1024);
+        CHECK(m.bytes == 12 * 84 && m.rgs == 1);
+    }
     CHECK(!planes_fit_u32(llmi::T_Q5_K, INT32_MAX, (int64_t)INT32_MAX / 256 * 256));
     CHECK(!planes_fit_u32(llmi::T_Q8_0, INT64_MAX / 2, (int64_t)1 << 40) && planes_fit_u32(llmi::T_F32, INT32_MAX, INT32_MAX));
     CHECK(planes_fit_u32(llmi::T_Q4_K, 128256, 8192) && llmi::layout_rgs(llmi::T_Q4_K, 1004, 512) == 2);

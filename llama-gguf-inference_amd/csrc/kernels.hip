@@ -215,6 +215,24 @@ __global__ void k_repack_kq(int type, const uint8_t* raw, uint8_t* A, uint8_t* H
             Dp[b * 2] = x[108];
             Dp[b * 2 + 1] = x[109];
         }
+    } else if (type == T_Q2_K) {
+        // Q3_K's A plane (common.h): A part c, dword m, byte i, field j = 2 hi + k: the quant of
+        // chunk element 32 hi + 4k + m + 8i.  S dword c: native scales[4c + {0, 2, 1, 3}]; D: d, dmin
+        const uint8_t* x = raw + b * 84;
+        const uint8_t* qs = x + 16;
+        auto q = [&](int w) -> int { return (qs[32 * (w >> 7) + (w & 31)] >> (2 * ((w >> 5) & 3))) & 3; };
+        uint8_t* ap = A + piece_off((uint32_t)row, (uint32_t)c, (uint32_t)u, (uint32_t)U, 4, rgs);
+        for (int m = 0; m < 4; ++m)
+            for (int i = 0; i < 4; ++i) {
+                uint8_t v = 0;
+                for (int j = 0; j < 4; ++j) v |= (uint8_t)(q(64 * c + 32 * (j >> 1) + 4 * (j & 1) + m + 8 * i) << (2 * j));
+                ap[4 * m + i] = v;
+            }
+        S[b * 16 + 4 * c] = x[4 * c];
+        S[b * 16 + 4 * c + 1] = x[4 * c + 2];
+        S[b * 16 + 4 * c + 2] = x[4 * c + 1];
+        S[b * 16 + 4 * c + 3] = x[4 * c + 3];
+        Dp[b * 4 + c] = x[80 + c];
     } else {  // Q6_K
         const uint8_t* x = raw + b * 210;
         const uint8_t* ql = x;
@@ -341,6 +359,8 @@ static hipError_t mv_dispatch_qkv2(const MVArgs& a, dim3 grid, size_t lds, hipSt
         LLMI_QKV2(T_Q4_K, T_Q6_K) LLMI_QKV2(T_Q4_K, T_Q5_K) LLMI_QKV2(T_Q5_K, T_Q6_K)
         if constexpr (!X86) {  // Q3_K_M files: q / k in Q3_K, attn_v in Q4_K or Q5_K
             LLMI_QKV2(T_Q3_K, T_Q4_K) LLMI_QKV2(T_Q3_K, T_Q5_K)
+            // Q2_K files: q / k in Q2_K, attn_v in Q3_K or Q4_K
+            LLMI_QKV2(T_Q2_K, T_Q3_K) LLMI_QKV2(T_Q2_K, T_Q4_K)
         }
     }
 #undef LLMI_QKV2
@@ -369,6 +389,9 @@ static hipError_t mv_dispatch_type(const MVArgs& a, int epi, dim3 grid, size_t l
         case T_Q3_K:
             if constexpr (X86) return hipErrorNotSupported;  // no x86 association of Q3_K (model.cpp refuses the load)
             else return mv_dispatch_epi<0, NORM, T_Q3_K, 0>(a, epi, grid, lds, s);
+        case T_Q2_K:
+            if constexpr (X86) return hipErrorNotSupported;  // generic numerics only, as Q3_K
+            else return mv_dispatch_epi<0, NORM, T_Q2_K, 0>(a, epi, grid, lds, s);
         case T_Q8_0: return mv_dispatch_epi<1, NORM, T_Q8_0, X86>(a, epi, grid, lds, s);
         default: return hipErrorInvalidValue;
     }
@@ -599,7 +622,7 @@ hipError_t launch_repack(int type, const void* raw, uint8_t* a, uint8_t* h, uint
                          int64_t cols, int rgs, int x86, hipStream_t s) {
     if (nblk <= 0) return hipSuccess;
     if (cols % 256) return hipErrorInvalidValue;
-    if (type == T_Q3_K && x86) return hipErrorInvalidValue;  // Q3_K: generic numerics only
+    if ((type == T_Q3_K || type == T_Q2_K) && x86) return hipErrorInvalidValue;  // Q3_K, Q2_K: generic numerics only
     if (is_kquant(type)) {
         const int64_t thr = nblk * 4;
         hipLaunchKernelGGL(k_repack_kq, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, type, (const uint8_t*)raw, a,

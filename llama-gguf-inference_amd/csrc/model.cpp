@@ -63,6 +63,7 @@ static size_t region_end(const DevMat& m) {
     switch (m.type) {
         case T_Q4_K: case T_Q5_K: return m.off_s + nblk * 16;
         case T_Q3_K: case T_Q6_K: case T_Q8_0: return m.off_d + nblk * 2;
+        case T_Q2_K: return m.off_d + nblk * 4;
         default: return m.off_a + m.bytes;
     }
 }
@@ -149,12 +150,14 @@ bool model_load(const std::string& path, int device, bool vocab_only, bool no_up
         return false;
     }
     if (E % 256 || hp.n_ff % 256) { err = "n_embd and n_ff must be multiples of 256"; return false; }
-    // Q3_K has the generic order only: upstream's x86 vec_dot_q3_K_q8_K associates differently
-    // and nothing restates it, so such a model is refused, never decoded in the wrong order
+    // Q3_K and Q2_K have the generic order only: upstream's x86 vec_dot_q3_K_q8_K / vec_dot_q2_K_q8_K
+    // associate differently and nothing restates them, so such a model is refused, never decoded
+    // in the wrong order
     if (M.numerics == NUMERICS_X86)
         for (const GgufTensor& t : f.tensors)
-            if (t.type == T_Q3_K) {
-                err = "tensor " + t.name + ": weight type q3_K is not supported in x86 numerics (generic numerics only)";
+            if (t.type == T_Q3_K || t.type == T_Q2_K) {
+                err = "tensor " + t.name + ": weight type " + type_name(t.type) +
+                      " is not supported in x86 numerics (generic numerics only)";
                 return false;
             }
     auto chk = [&](const DevMat& m, int64_t rows, int64_t cols, const char* nm, bool quant) {
@@ -289,10 +292,10 @@ bool model_upload(Model& M, std::string& err, const UploadHook* hook) {
             const size_t row_raw = (size_t)bpr * block_bytes(m.type);
             // chunks of whole row groups (common.h): a multiple of 64 rows
             const int64_t rows_per = std::max<int64_t>(64, (int64_t)(kChunk / row_raw) / 64 * 64);
-            const size_t pa = m.type == T_Q8_0 ? 32 : m.type == T_Q3_K ? 64 : 128,
+            const size_t pa = m.type == T_Q8_0 ? 32 : (m.type == T_Q3_K || m.type == T_Q2_K) ? 64 : 128,
                          ph = (m.type == T_Q5_K || m.type == T_Q3_K) ? 32 : m.type == T_Q6_K ? 64 : 0,
                          ps = m.type == T_Q8_0 ? 0 : m.type == T_Q3_K ? 12 : 16,
-                         pd = (m.type == T_Q6_K || m.type == T_Q8_0 || m.type == T_Q3_K) ? 2 : 0;
+                         pd = (m.type == T_Q6_K || m.type == T_Q8_0 || m.type == T_Q3_K) ? 2 : m.type == T_Q2_K ? 4 : 0;
             for (int64_t r0 = 0; r0 < m.rows && e == hipSuccess; r0 += rows_per) {
                 const int64_t nr = std::min(rows_per, m.rows - r0);
                 const size_t n = (size_t)nr * row_raw;

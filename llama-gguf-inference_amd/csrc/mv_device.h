@@ -490,12 +490,12 @@ __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMI
 __device__ __forceinline__ uint32_t q6_hi_bytes(uint32_t sel) { return __builtin_amdgcn_perm(0xF0E01000u, 0xF0E01000u, sel); }
 
 template <int T>
-__host__ __device__ constexpr int unit_parts() { return T == T_Q8_0 ? 16 : T == T_Q3_K ? 4 : 8; }
+__host__ __device__ constexpr int unit_parts() { return T == T_Q8_0 ? 16 : (T == T_Q3_K || T == T_Q2_K) ? 4 : 8; }
 template <int T>
 __host__ __device__ constexpr int unit_hparts() { return T == T_Q6_K ? 4 : (T == T_Q5_K || T == T_Q3_K) ? 2 : 1; }
 // plane bytes per unit (row strides are U times these)
 template <int T>
-__host__ __device__ constexpr uint32_t unit_abytes() { return T == T_Q8_0 ? 256u : T == T_Q3_K ? 64u : 128u; }
+__host__ __device__ constexpr uint32_t unit_abytes() { return T == T_Q8_0 ? 256u : (T == T_Q3_K || T == T_Q2_K) ? 64u : 128u; }
 
 // byte offset of 16-B piece (row, part p, unit u) of an A / H plane with np parts per
 // unit, rows in groups of 2^rgs (common.h ROW GROUPS)
@@ -508,9 +508,10 @@ __host__ __device__ __forceinline__ uint32_t piece_off(uint32_t row, uint32_t p,
 template <int T>
 struct UnitW {
     u32x4 q[unit_parts<T>()];   // quant parts
-    u32x4 s;                    // Q4_K/Q5_K header; Q6_K 16 scales; Q8_0 eight fp16 d; Q3_K .x .y .z the 12 scale bytes
+    u32x4 s;                    // Q4_K/Q5_K header; Q6_K 16 scales; Q8_0 eight fp16 d; Q3_K .x .y .z the 12 scale bytes;
+                                // Q2_K the 16 scale/min bytes (S plane order, common.h)
     u32x4 h[unit_hparts<T>()];  // Q5_K fifth bits (2 x 16 B); Q6_K 2-bit highs (4 x 16 B); Q3_K inverted high bits (2 x 16 B)
-    uint32_t d;                 // Q6_K / Q3_K fp16 d
+    uint32_t d;                 // Q6_K / Q3_K fp16 d; Q2_K fp16 d | fp16 dmin << 16
 };
 
 // Unit u of row `row` of a segment.  Loads are unconditional (callers clamp row and
@@ -532,6 +533,9 @@ __device__ __forceinline__ UnitW<T> load_unit(const Seg& sg, uint32_t row, uint3
         w.h[0] = ldw(sg.h + oh);
         w.h[1] = ldw(sg.h + oh + P);
         w.d = *(const uint16_t*)(sg.d + ru * 2);
+    } else if constexpr (T == T_Q2_K) {  // 84 B per unit: 4 parts, 16 scale/min bytes, {d, dmin}
+        w.s = ldw(sg.s + ru * 16);
+        w.d = ldw4(sg.d + ru * 4);
     } else {
         w.s = ldw(sg.s + ru * 16);
         if constexpr (T == T_Q5_K || T == T_Q6_K) {
@@ -644,6 +648,52 @@ __device__ __forceinline__ void q3_terms(const UnitW<T_Q3_K>& w, const uint8_t* 
     tm[8] = 0.f;
 }
 
+// ---- Q2_K (generic numerics only; layout: common.h) ----
+// ggml's generic vec_dot_q2_K_q8_K per block: isum = sum over the sixteen sub-blocks of
+// (scale & 15) * sum a q, summs = sum bsums * (scale >> 4), then ONE fp32 term
+//     (d_a d) (float)isum - (d_a dmin) (float)summs
+// added onto the row's single chain sumf (no residue chains).  Per field dword (chunk c, dword m,
+// field j = 2 hi + k): mask the four 2-bit quants into bytes, one packed 16-bit multiply by the
+// scale pair of sub-blocks 4c + 2 hi, + 1 (bytes 0,1 | 2,3: each byte scale q <= 45, no carry: the
+// 16-bit products stay below 771 * 15), one v_dot4 against the whole dword m of activation part
+// 2c + k, LO or HI by hi, accumulating: |dot| <= 4 * 45 * 127, 64 of them < 2^21.  Four
+// accumulators (by m) keep the dots independent.  summs: the record's int16 bsum pairs against
+// the min pairs, eight v_dot2.
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t q2_scaled(uint32_t field, uint32_t pair) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, field) * __builtin_bit_cast(u16x2, pair));
+}
+__device__ __forceinline__ float q2_term(const UnitW<T_Q2_K>& w, const uint8_t* rec) {
+    constexpr uint32_t MP = 0x000F000Fu;
+    int is[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t sp[2] = {w.s[c] & MP, (w.s[c] >> 8) & MP};  // scale pairs of hi = 0, 1
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const i32x4 alo = *(const i32x4*)(rec + 32 * (2 * c + k)), ahi = *(const i32x4*)(rec + 32 * (2 * c + k) + 16);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const uint32_t q = w.q[c][m];
+                is[m] = dot4(q2_scaled((q >> (2 * k)) & M2, sp[0]), alo[m], is[m]);
+                is[m] = dot4(q2_scaled((q >> (4 + 2 * k)) & M2, sp[1]), ahi[m], is[m]);
+            }
+        }
+    }
+    const int isum = (is[0] + is[1]) + (is[2] + is[3]);
+    const i32x4 b0 = *(const i32x4*)(rec + kRecBs), b1 = *(const i32x4*)(rec + kRecBs + 16);
+    int summs = 0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {  // sub-blocks 2t, 2t + 1: S dword t / 2, half t % 2
+        const uint32_t mm = (w.s[t >> 1] >> (8 * (t & 1) + 4)) & MP;
+        const int bp = t < 4 ? b0[t] : b1[t - 4];
+        summs = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, bp), __builtin_bit_cast(short2_t, mm), summs, false);
+    }
+    const float da = *(const float*)(rec + kRecD);
+    const float dall = da * h2f(w.d), dmn = da * h2f(w.d >> 16);
+    return dall * (float)isum - dmn * (float)summs;
+}
+
 // The unit's terms against activation record `rec` (kRec layout): K-quants tm[l] =
 // d*(float)aux32[l] (l < 8), tm[8] = -(dmin*(float)sumi) (Q6_K: +0, there is no min
 // chain and sumf starts at 0); Q8_0 tm[b] = (float)sumi_b * (d_w * d_a), b < 8.
@@ -749,6 +799,14 @@ __device__ __forceinline__ void unit_terms(const UnitW<T>& w, const uint8_t* rec
         tm[8] = 0.f;
     } else if constexpr (T == T_Q3_K) {
         q3_terms<false, DZ>(w, rec, *(const float*)(rec + kRecD), tm);
+    } else if constexpr (T == T_Q2_K) {
+        // one term per block, on the sumf chain (tm[8]); the eight residue chains stay +0, and
+        // adding them in row_final changes no bit: sumf starts at +0 and x + y is -0 only when
+        // both are -0, so no chain value is ever -0, and v + (+0) == v for every other v
+        // (DESIGN.md "The Q2_K unit")
+#pragma unroll
+        for (int l = 0; l < 8; ++l) tm[l] = 0.f;
+        tm[8] = q2_term(w, rec);
     } else {
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
@@ -1473,6 +1531,7 @@ __device__ __forceinline__ void task_any(const MA& A, const Lds& L, float* F, co
                 case T_Q4_K: unit_terms<T_Q4_K>(load_unit<T_Q4_K>(sg, lu.row, lu.u, g.U), rec, tm); break;
                 case T_Q5_K: unit_terms<T_Q5_K>(load_unit<T_Q5_K>(sg, lu.row, lu.u, g.U), rec, tm); break;
                 case T_Q3_K: unit_terms<T_Q3_K>(load_unit<T_Q3_K>(sg, lu.row, lu.u, g.U), rec, tm); break;
+                case T_Q2_K: unit_terms<T_Q2_K>(load_unit<T_Q2_K>(sg, lu.row, lu.u, g.U), rec, tm); break;
                 default: unit_terms<T_Q6_K>(load_unit<T_Q6_K>(sg, lu.row, lu.u, g.U), rec, tm); break;
             }
         }
@@ -1716,6 +1775,16 @@ __device__ __forceinline__ float dequant_elem(const Seg& w, int row, int e, int 
             const int sc = q3_sc(q3_scales(s0, s1, s2)[c], t >> 4 & 3);
             const float d = h2f(*(const uint16_t*)(w.d + ru * 2));
             return d * (float)sc * (float)(lo - 4 * hb);
+        }
+        case T_Q2_K: {  // A as Q3_K's; S dword c = native scales[4c + {0, 2, 1, 3}]; D = {d, dmin} (common.h)
+            const int t = e & 255, c = t >> 6, hi = (t >> 5) & 1, l = t & 7, i = (t & 31) >> 3, k = l >> 2, m = l & 3;
+            const int q = (w.a[piece_off(row, c, u, U, 4, w.rgs) + 4 * m + i] >> (2 * (2 * hi + k))) & 3;
+            const int sb = (t >> 4) & 3;  // sub-block 4c + sb: byte {0, 2, 1, 3}[sb] of the dword
+            const uint8_t sc = w.s[ru * 16 + 4 * c + ((sb & 1) << 1 | sb >> 1)];
+            const uint32_t dd = *(const uint32_t*)(w.d + ru * 4);
+            // upstream dequantize_row_q2_K: dl = d * (sc & 0xF), ml = dmin * (sc >> 4), y = dl * q - ml
+            const float dl = h2f(dd) * (float)(sc & 15), ml = h2f(dd >> 16) * (float)(sc >> 4);
+            return dl * (float)q - ml;
         }
         case T_Q4_K:
         case T_Q5_K:

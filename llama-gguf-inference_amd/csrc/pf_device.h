@@ -55,7 +55,7 @@ __device__ __forceinline__ RowPtr row_ptr(const Seg& s, int row, int cols) {
     r.qa = s.a + piece_off((uint32_t)row, 0, 0, U, unit_parts<T>(), s.rgs);
     r.hb = s.h + piece_off((uint32_t)row, 0, 0, U, unit_hparts<T>(), s.rgs);
     r.sb = s.s + ru * (T == T_Q3_K ? 12 : 16);
-    r.db = s.d + ru * (T == T_Q8_0 ? 16 : 2);
+    r.db = s.d + ru * (T == T_Q8_0 ? 16 : T == T_Q2_K ? 4 : 2);
     return r;
 }
 // plain (temporal) loads: a lane reads 16 B of a 128-B line whose other 112 B the next 7
@@ -95,6 +95,12 @@ __device__ __forceinline__ PfW<T> pf_w_load(const RowPtr& rp, int stage, int) {
         w.hdr = h >> (g & 1);
         w.q1 = u32x4{pf_ld4(rp.sb + st * 12), pf_ld4(rp.sb + st * 12 + 4), pf_ld4(rp.sb + st * 12 + 8), 0u};
         w.d = *(const uint16_t*)(rp.db + st * 2);
+    } else if constexpr (T == T_Q2_K) {
+        // chunk g: A part g; sc = S dword g (scales / mins of sub-blocks 4g + {0, 2, 1, 3});
+        // d = fp16 d | fp16 dmin << 16 (common.h)
+        w.q0 = pf_ld16(rp.qa + g * rp.ps + st * 16);
+        w.sc = pf_ld4(rp.sb + st * 16 + 4 * g);
+        w.d = pf_ld4(rp.db + st * 4);
     } else {
         w.q0 = pf_ld16(rp.qa + (2 * g) * rp.ps + st * 16);
         w.q1 = pf_ld16(rp.qa + (2 * g + 1) * rp.ps + st * 16);
@@ -161,6 +167,25 @@ __device__ __forceinline__ void pf_build_b(const PfW<T>& w, int l, h2 slo, h2 sh
             const uint32_t x01 = __builtin_amdgcn_perm(0u, y, 0x0c010c00u), x23 = __builtin_amdgcn_perm(0u, y, 0x0c030c02u);
             const h2 off = h2{(_Float16)1028.f, (_Float16)1028.f};
             const h2 a = (as_h2(pf_magic(x01)) - off) * s6[2 * hi], b = (as_h2(pf_magic(x23)) - off) * s6[2 * hi + 1];
+            r[4 * hi] = a[0];
+            r[4 * hi + 1] = a[1];
+            r[4 * hi + 2] = b[0];
+            r[4 * hi + 3] = b[1];
+        }
+        out[0] = r;
+    } else if constexpr (T == T_Q2_K) {
+        // residue l = 4k + m: fields k (LO) and 2 + k (HI) of dword m, each times the scale pair
+        // of its sub-blocks by the packed 16-bit multiply (q2_scaled): bytes (scale & 15) q <= 45,
+        // exact f16 by the magic number minus 1024.  Pairs as Q6_K's: LO bytes 0,1 sub-block 4g,
+        // bytes 2,3 4g + 1, HI 4g + 2, 4g + 3
+        const int k = l >> 2, m = l & 3;
+        const h2 off = h2{(_Float16)1024.f, (_Float16)1024.f};
+        h8 r;
+#pragma unroll
+        for (int hi = 0; hi < 2; ++hi) {
+            const uint32_t y = q2_scaled((w.q0[m] >> (4 * hi + 2 * k)) & M2, (w.sc >> (8 * hi)) & 0x000F000Fu);
+            const uint32_t x01 = __builtin_amdgcn_perm(0u, y, 0x0c010c00u), x23 = __builtin_amdgcn_perm(0u, y, 0x0c030c02u);
+            const h2 a = as_h2(pf_magic(x01)) - off, b = as_h2(pf_magic(x23)) - off;
             r[4 * hi] = a[0];
             r[4 * hi + 1] = a[1];
             r[4 * hi + 2] = b[0];

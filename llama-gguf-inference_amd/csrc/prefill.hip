@@ -405,6 +405,18 @@ __global__ __launch_bounds__(256, T == T_Q8_0 ? 1 : 2) void k_pf_gemm(PfGemm g) 
                         const _Float16 fs = (_Float16)(float)q3_sc(s4, k);
                         s6[k] = h2{fs, fs};
                     }
+                } else if constexpr (T == T_Q2_K) {
+                    // the scales go into the B fragments (pf_build_b); bm = the mins of sub-blocks
+                    // 4 grp + {0, 0, 1, 1, 2, 2, 3, 3}, the sub-blocks of a fragment's eight
+                    // elements (S dword grp holds sub-blocks 4 grp + {0, 2, 1, 3}, common.h)
+                    dw = h2f(wcur.d);
+                    dmw = h2f(wcur.d >> 16);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const _Float16 fm = (_Float16)(float)((wcur.sc >> (8 * ((k & 1) << 1 | k >> 1) + 4)) & 15u);
+                        bm[2 * k] = fm;
+                        bm[2 * k + 1] = fm;
+                    }
                 } else {  // Q6_K: sc = 16 sh + sl per sub-block 4 grp + k
                     dw = h2f(wcur.d);
 #pragma unroll
@@ -424,6 +436,36 @@ __global__ __launch_bounds__(256, T == T_Q8_0 ? 1 : 2) void k_pf_gemm(PfGemm g) 
                     const int t0 = 16 * (p >> 1) + tq + 2 * (p & 1);
                     d[p] = mul2(f2v{dw, dw}, f2v{Lda[t0], Lda[t0 + 1]});
                 }
+                if constexpr (T == T_Q2_K) {
+                    // ggml's generic vec_dot_q2_K_q8_K: one term per block on the single chain
+                    // sumf.  isum = the eight residues' MFMAs accumulated (integers below 2^21:
+                    // exact), summs = sum over the block's elements of min(sub-block) * a, which
+                    // is sum bsums * min, on the same activation fragments against bm.
+                    f4 qi[NTL], qm[NTL];
+#pragma unroll
+                    for (int tl = 0; tl < NTL; ++tl) qi[tl] = qm[tl] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int l = 0; l < 8; ++l) {
+                        h8 bf;
+                        pf_build_b<T, X86>(wcur, l, slo, shi, slo_o, shi_o, s6, s6o, &bf);
+#pragma unroll
+                        for (int tl = 0; tl < NTL; ++tl) {
+                            const h8 af = afrag(l, tl);
+                            qi[tl] = mfma16(af, bf, qi[tl]);
+                            qm[tl] = mfma16(af, bm, qm[tl]);
+                        }
+                    }
+#pragma unroll
+                    for (int tl = 0; tl < NTL; ++tl)
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {  // sumf += (d_a d) isum - (d_a dmin) summs
+                            const int t0 = 16 * tl + tq + 2 * h;
+                            const f2v dm = mul2(f2v{Lda[t0], Lda[t0 + 1]}, f2v{dmw, dmw});
+                            const f2v term = sub2(mul2(d[2 * tl + h], f2v{qi[tl][2 * h], qi[tl][2 * h + 1]}),
+                                                  mul2(dm, f2v{qm[tl][2 * h], qm[tl][2 * h + 1]}));
+                            sumf[2 * tl + h] = add2(sumf[2 * tl + h], term);
+                        }
+                } else {
 #pragma unroll
                 for (int l = 0; l < 8; ++l) {
                     h8 bf[2];
@@ -450,6 +492,7 @@ __global__ __launch_bounds__(256, T == T_Q8_0 ? 1 : 2) void k_pf_gemm(PfGemm g) 
                                 sums[l][2 * tl + h] = add2(sums[l][2 * tl + h], mul2(d[2 * tl + h], f2v{acc[2 * h], acc[2 * h + 1]}));
                         }
                     }
+                }
                 }
                 if constexpr (X86 && T == T_Q4_K) {  // acc_m[k] = fma(-d_a * dmin_w, (float)prod[k], acc_m[k]), prod[k] = lane group k's slice
 #pragma unroll
@@ -478,7 +521,7 @@ __global__ __launch_bounds__(256, T == T_Q8_0 ? 1 : 2) void k_pf_gemm(PfGemm g) 
                             sumf[2 * tl + h] = fma2(dm, f2v{si[2 * h], si[2 * h + 1]}, sumf[2 * tl + h]);
                         }
                     }
-                } else if constexpr (T != T_Q6_K && T != T_Q3_K) {  // sumf -= (dmin * d_a) * sumi; sumi = mins . bsum pairs on the MFMA (exact)
+                } else if constexpr (T != T_Q6_K && T != T_Q3_K && T != T_Q2_K) {  // sumf -= (dmin * d_a) * sumi; sumi = mins . bsum pairs on the MFMA (exact)
 #pragma unroll
                     for (int tl = 0; tl < NTL; ++tl) {
                         const h8 af = *(const h8*)(Lbf + (tl >> 1) * 2048 + ((size_t)grp * 32 + 16 * (tl & 1) + (lane & 15)) * 16);
@@ -503,7 +546,7 @@ __global__ __launch_bounds__(256, T == T_Q8_0 ? 1 : 2) void k_pf_gemm(PfGemm g) 
                     v = add2(add2(t0, t2), add2(t1, t3));
                     if constexpr (T == T_Q4_K) v = add2(v, add2(add2(accm[0][p], accm[2][p]), add2(accm[1][p], accm[3][p])));
                     if constexpr (T == T_Q5_K) v = add2(v, sumf[p]);
-                } else if constexpr (T != T_Q8_0) {
+                } else if constexpr (T != T_Q8_0 && T != T_Q2_K) {  // (Q2_K: the residue chains are +0, mv_device.h)
 #pragma unroll
                     for (int l = 0; l < 8; ++l) v = add2(v, sums[l][p]);
                 }
@@ -1211,8 +1254,8 @@ static hipError_t pf_gemm_launch(const PfGemm& g0, hipStream_t s) {
     const PfGemm& g = g0;
 #endif
     if (g.w.x86) {  // x86 numerics: 32-token workgroups (the 8-12 chains per row: register room)
-        if constexpr (T == T_Q3_K) {
-            return hipErrorNotSupported;  // Q3_K: generic numerics only
+        if constexpr (T == T_Q3_K || T == T_Q2_K) {
+            return hipErrorNotSupported;  // Q3_K, Q2_K: generic numerics only
         } else {
             const dim3 grid((g.rows + kPfRows - 1) / kPfRows, (g.T + 31) / 32);
             PfGemm gx = g;
@@ -1250,11 +1293,12 @@ static hipError_t pf_gemm_epi(const PfGemm& g, int epi, hipStream_t s) {
 }
 bool pf_gemm_ok(int type, int rows, int cols) {
     if (rows % 16 || rows <= 0 || cols % 256 || cols <= 0) return false;
-    return type == T_Q3_K || type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0;
+    return type == T_Q2_K || type == T_Q3_K || type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q8_0;
 }
 hipError_t launch_pf_gemm(const PfGemm& g, int epi, hipStream_t s) {
     if (!pf_gemm_ok(g.w.type, g.rows, g.cols) || g.T <= 0) return hipErrorInvalidValue;
     switch (g.w.type) {
+        case T_Q2_K: return pf_gemm_epi<T_Q2_K>(g, epi, s);
         case T_Q3_K: return pf_gemm_epi<T_Q3_K>(g, epi, s);
         case T_Q4_K: return pf_gemm_epi<T_Q4_K>(g, epi, s);
         case T_Q5_K: return pf_gemm_epi<T_Q5_K>(g, epi, s);

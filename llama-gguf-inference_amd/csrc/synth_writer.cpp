@@ -48,6 +48,8 @@ bool get_preset(const std::string& p, Preset& out) {
     else if (p == "mistral7b-q5km") out = {p, 4096, 32, 32, 8, 14336, 32000, 32768, 1000000.f, 1e-5f, 17, true};
     else if (p == "llama3-8b-q3km") out = {p, 4096, 32, 32, 8, 14336, 128256, 8192, 500000.f, 1e-5f, 12, false};
     else if (p == "tiny-q3km") out = {p, 512, 16, 4, 2, 768, 777, 512, 500000.f, 1e-5f, 12, false};
+    else if (p == "llama3-8b-q2k") out = {p, 4096, 32, 32, 8, 14336, 128256, 8192, 500000.f, 1e-5f, 10, false};
+    else if (p == "tiny-q2k") out = {p, 512, 16, 4, 2, 768, 777, 512, 500000.f, 1e-5f, 10, false};
     else if (p == "tiny-mixed") out = {p, 256, 2, 4, 2, 512, 1000, 512, 10000.f, 1e-5f, 1, true};
     else if (p == "tiny-mixed-d128") out = {p, 512, 2, 4, 2, 768, 777, 512, 500000.f, 1e-5f, 1, false};
     else return false;
@@ -69,11 +71,16 @@ std::vector<TSpec> tensor_table(const Preset& P) {
     // ffn_down (Q5_K in the first sixteenth of the layers, then Q4_K) and output (Q6_K)
     const bool q3km = P.name == "llama3-8b-q3km" || P.name == "tiny-q3km";
     if (q3km) emb = T_Q3_K;
+    // Q2_K (file_type 10; upstream's mix, recalled and approximated): Q2_K for token_embd, attn_q,
+    // attn_k, ffn_gate and ffn_up; Q3_K for attn_v, attn_output and ffn_down; Q6_K for output
+    const bool q2k = P.name == "llama3-8b-q2k" || P.name == "tiny-q2k";
+    if (q2k) emb = T_Q2_K;
     t.push_back({"token_embd.weight", emb, E, V, false});
     for (int l = 0; l < P.L; ++l) {
         int q = T_Q4_K, k = T_Q4_K, v = T_Q4_K, o = T_Q4_K, g = T_Q4_K, u = T_Q4_K, d = T_Q4_K;
         const bool mb = more_bits(l, P.L);
         if (q3km) { q = k = g = u = T_Q3_K; v = l < 2 ? T_Q5_K : T_Q4_K; d = l < (P.L + 15) / 16 ? T_Q5_K : T_Q4_K; }
+        else if (q2k) { q = k = g = u = T_Q2_K; v = o = d = T_Q3_K; }
         else if (P.name == "llama3-8b-q4km") { v = d = mb ? T_Q6_K : T_Q4_K; }
         else if (P.name == "llama3-70b-q4km") { v = mb ? T_Q6_K : T_Q5_K; d = mb ? T_Q6_K : T_Q4_K; }
         else if (P.name == "tinyllama-q8_0") { q = k = v = o = g = u = d = T_Q8_0; }

@@ -18,13 +18,13 @@ from ._lib import (POOLING_CLS, POOLING_LAST, POOLING_MEAN, POOLING_NONE, POOLIN
                    POOLING_UNSPECIFIED)
 
 # ggml type ids
-F32, F16, Q8_0, Q3_K, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 8, 11, 12, 13, 14, 15
+F32, F16, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 8, 10, 11, 12, 13, 14, 15
 # model numerics (llama_model_params.numerics): ggml's generic scalar order, or upstream's
 # x86 AVX2 association (the reference's NGL=0 build)
 NUMERICS_GENERIC, NUMERICS_X86, NUMERICS_FA = 0, 1, 2  # NUMERICS_FA is OR-ed into either (llmi.h)
 PRESETS = (
     "llama3-8b-q4km", "llama3-70b-q4km", "tinyllama-q8_0", "mistral7b-q6k", "mistral7b-q5km",
-    "tiny-mixed", "tiny-mixed-d128", "llama3-8b-q3km", "tiny-q3km",
+    "tiny-mixed", "tiny-mixed-d128", "llama3-8b-q3km", "tiny-q3km", "llama3-8b-q2k", "tiny-q2k",
 )
 
 

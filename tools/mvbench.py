@@ -9,12 +9,13 @@ import torch
 from llmi._lib import lib
 from helpers import random_blocks, Q4_K, Q5_K, Q6_K, Q8_0
 from q3k_cases import Q3_K, random_q3k, twin_q6k
+from q2k_cases import Q2_K, random_q2k
 L = lib()
 P = lambda t: C.c_void_p(t.data_ptr())
 res = {}
 shapes = [(Q4_K, 28672, 4096), (Q4_K, 4096, 14336), (Q6_K, 4096, 14336), (Q6_K, 128256, 4096), (Q4_K, 6144, 4096),
           (Q5_K, 14336, 4096), (Q8_0, 5632, 2048)]
-if os.environ.get("MV_SHAPES"):  # e.g. "12:28672x4096,14:128256x4096"; 11 = Q3_K, 11t = the Q6_K twin of that matrix
+if os.environ.get("MV_SHAPES"):  # e.g. "12:28672x4096,14:128256x4096"; 10 = Q2_K, 11 = Q3_K, 11t = the Q6_K twin of that matrix
     shapes = []
     for tok in os.environ["MV_SHAPES"].split(","):
         t, rc = tok.split(":"); r, c = rc.split("x")
@@ -25,7 +26,10 @@ rng = np.random.default_rng(0)
 for qt, rows, cols in shapes:
     key = f"{qt}:{rows}x{cols}"
     # (11 and 11t: a seed of their own, so that both hold the same matrix)
-    blocks = random_q3k(rows, cols, np.random.default_rng(11)) if qt in (Q3_K, "11t") else random_blocks(qt, rows, cols, rng)
+    if qt == Q2_K:
+        blocks = random_q2k(rows, cols, np.random.default_rng(10))
+    else:
+        blocks = random_q3k(rows, cols, np.random.default_rng(11)) if qt in (Q3_K, "11t") else random_blocks(qt, rows, cols, rng)
     if qt == "11t":
         qt, blocks = Q6_K, twin_q6k(blocks)
     lb = L.llmi_device_layout_bytes(qt, rows, cols)
