@@ -29,12 +29,26 @@
 #ifndef LLMI_BMD_Q3K_BUFS
 #define LLMI_BMD_Q3K_BUFS 1
 #endif
+// batch_q2k.hip includes this file with LLMI_BATCH_Q2K = 1: the T_Q2_K instantiations, behind
+// mvn_q2k / bmm_q2k / bmm2_q2k.  LLMI_BMD_Q2K_BUFS: the same A/B for k_bmd<T_Q2_K> (its round
+// buffer is 10 KB; two buffers were not measured, one ships)
+#ifndef LLMI_BATCH_Q2K
+#define LLMI_BATCH_Q2K 0
+#endif
+#ifndef LLMI_BMD_Q2K_BUFS
+#define LLMI_BMD_Q2K_BUFS 1
+#endif
+// a per-type unit: the shared kernels and launchers below compile in batch.hip's own unit only
+#define LLMI_BATCH_SUB (LLMI_BATCH_Q3K || LLMI_BATCH_Q2K)
 
 namespace llmi {
 
 hipError_t mvn_q3k(const MVArgs& a, int epi, int nt, int max_blocks, hipStream_t s);
 hipError_t bmm_q3k(const MVArgs& a, int epi, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s);
 hipError_t bmm2_q3k(const MVArgs& a1, const MVArgs& a2, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s);
+hipError_t mvn_q2k(const MVArgs& a, int epi, int nt, int max_blocks, hipStream_t s);
+hipError_t bmm_q2k(const MVArgs& a, int epi, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s);
+hipError_t bmm2_q2k(const MVArgs& a1, const MVArgs& a2, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s);
 
 namespace {
 
@@ -238,7 +252,7 @@ __global__ __launch_bounds__(kBT) void k_mvn(MVArgs A) {
 
 // batched step entry: per slot (blockIdx.y) the token (host-provided for this position,
 // else the argmax of the sequence's previous step), the sequence state, the embedding row
-#if !LLMI_BATCH_Q3K
+#if !LLMI_BATCH_SUB
 __global__ __launch_bounds__(256) void k_bembed(BEmbArgs a) {
     const int s = blockIdx.y;
     const int seq = a.tseq[s];
@@ -287,12 +301,18 @@ constexpr int kBmW = 8, kBmT = kBmW * 64;
 // chains per (row, token): generic 8 residues + sumf (Q6_K, Q3_K: no mins); x86 (X86 = 1, model
 // numerics LLMI_NUMERICS_X86) the 8 AVX2 lanes + Q4_K's 4 min lanes / Q5_K's summs.  A
 // round buffer holds bm_ns() term slots per (stage, matrix): generic 9, x86 one per chain.
+// Q2_K (generic only): ggml's dot has ONE chain, sumf, with one term per block; the single-token
+// fold's eight residue chains receive +0 and change no bit (DESIGN.md "Q2_K in the batched
+// kernels"), so here the type has 1 chain and 1 term slot: the LDS round trip and the fold
+// threads carry one term per (stage, matrix, row, token), not nine.
 template <int T>
 __host__ __device__ constexpr bool bm_nomins() { return T == T_Q6_K || T == T_Q3_K; }
 template <int T, int X86>
-__host__ __device__ constexpr int bm_nc() { return X86 ? (T == T_Q4_K ? 12 : T == T_Q5_K ? 9 : 8) : (bm_nomins<T>() ? 8 : 9); }
+__host__ __device__ constexpr int bm_nc() {
+    return X86 ? (T == T_Q4_K ? 12 : T == T_Q5_K ? 9 : 8) : T == T_Q2_K ? 1 : (bm_nomins<T>() ? 8 : 9);
+}
 template <int T, int X86>
-__host__ __device__ constexpr int bm_ns() { return X86 ? bm_nc<T, X86>() : 9; }
+__host__ __device__ constexpr int bm_ns() { return X86 ? bm_nc<T, X86>() : T == T_Q2_K ? 1 : 9; }
 
 template <int T, int NW>
 struct BmStage {
@@ -320,6 +340,11 @@ __device__ __forceinline__ void bm_load(BmStage<T, NW>& st, const RowPtr (&rp)[N
             st.w[wi].q1 = u32x4{pf_ld4(sp), pf_ld4(sp + 4), pf_ld4(sp + 8), 0u};
             st.w[wi].d = *(const uint16_t*)(rp[wi].db + (uint32_t)s * 2);
         }
+    } else if constexpr (T == T_Q2_K) {
+        // k_bmd: the stage's {d, dmin} dword (D plane, 4 B per unit) stays a global load, issued
+        // here a stage ahead with the activations; quants and the S plane come from the round buffer
+#pragma unroll
+        for (int wi = 0; wi < NW; ++wi) st.w[wi].d = pf_ld4(rp[wi].db + (uint32_t)s * 4);
     }
     // only the lanes of real tokens load (the padding rows' loads would repeat token 0's
     // fragments through the TA); the others keep zeros
@@ -340,7 +365,9 @@ __device__ __forceinline__ void bm_load(BmStage<T, NW>& st, const RowPtr (&rp)[N
             st.da[i] = ad[(size_t)t * S + s];
         }
     }
-    if constexpr (!bm_nomins<T>()) st.bs = n < ntl ? *(const h8*)(abf + pf_abf_off(n, s, grp, S)) : h8{};
+    // (Q2_K's mins are per 16 elements, the bsum fragment holds sums over 32: its summs comes
+    // from the activation fragments, bm_terms)
+    if constexpr (!bm_nomins<T>() && T != T_Q2_K) st.bs = n < ntl ? *(const h8*)(abf + pf_abf_off(n, s, grp, S)) : h8{};
 }
 
 // the stage's terms tm[wi][chain][i] (token 4 grp + i, row lane & 15).  X86: the chains'
@@ -382,6 +409,18 @@ __device__ __forceinline__ void bm_terms(const BmStage<T, NW>& st, float (&tm)[N
                 const _Float16 fs = (_Float16)(float)q3_sc(s4, k);
                 s6[k] = h2{fs, fs};
             }
+        } else if constexpr (T == T_Q2_K) {
+            // the scales ride in the B fragments (pf_build_b); bm = the mins of sub-blocks
+            // 4 grp + {0, 0, 1, 1, 2, 2, 3, 3}, those of a fragment's eight elements (S dword grp
+            // holds sub-blocks 4 grp + {0, 2, 1, 3}: prefill.hip's Q2_K branch)
+            dw = h2f(w.d);
+            dmw = h2f(w.d >> 16);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const _Float16 fm = (_Float16)(float)((w.sc >> (8 * ((k & 1) << 1 | k >> 1) + 4)) & 15u);
+                bm[2 * k] = fm;
+                bm[2 * k + 1] = fm;
+            }
         } else {  // Q6_K: sc = 16 sh + sl per sub-block 4 grp + k
             dw = h2f(w.d);
 #pragma unroll
@@ -402,6 +441,30 @@ __device__ __forceinline__ void bm_terms(const BmStage<T, NW>& st, float (&tm)[N
         for (int i = 0; i < 4; ++i) {
             d[i] = X86 ? 1.0f : dw * st.da[i];
             dm[i] = dmw * st.da[i];
+        }
+        if constexpr (T == T_Q2_K) {
+            // ggml's generic vec_dot_q2_K_q8_K: ONE term per block, (d_a d) isum - (d_a dmin) summs,
+            // two products and one subtraction (q2_term, mv_device.h).  isum: the eight residue
+            // MFMAs into one accumulator; |scale q a| <= 45 * 127, 256 of them < 2^21.  summs =
+            // sum over the block's elements of min(sub-block) a: a fragment's eight elements sit
+            // in the same four sub-blocks for every residue, so the eight activation fragments
+            // are added first (f16 integers, |sum| <= 8 * 127 = 1016 < 2048: exact) and ONE MFMA
+            // against bm follows: |min sum| <= 15 * 1016, 32 of them < 2^19.  Every product and
+            // partial sum is an integer below 2^24: exact in any order, as in prefill.hip
+            f4 qi{0.f, 0.f, 0.f, 0.f};
+            h8 asum = st.a[0];
+#pragma unroll
+            for (int l = 1; l < 8; ++l) asum += st.a[l];
+#pragma unroll
+            for (int l = 0; l < 8; ++l) {
+                h8 bf;
+                pf_build_b<T, X86>(w, l, slo, shi, slo_o, shi_o, s6, s6o, &bf);
+                qi = mfma16(st.a[l], bf, qi);
+            }
+            const f4 qm = mfma16(asum, bm, f4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tm[wi][0][i] = d[i] * qi[i] - dm[i] * qm[i];
+            continue;
         }
 #pragma unroll
         for (int l = 0; l < 8; ++l) {
@@ -487,6 +550,8 @@ __device__ __forceinline__ void bm_epilogue(const MVArgs& A, const float4* G, in
                     x = (t0 + t2) + (t1 + t3);
                     if constexpr (T == T_Q4_K) x = x + ((g(8) + g(10)) + (g(9) + g(11)));
                     if constexpr (T == T_Q5_K) x = x + g(8);
+                } else if constexpr (T == T_Q2_K) {
+                    x = g(0);  // sumf alone: the residue chains' + (+0) change no bit (bm_nc)
                 } else {
                     x = NC == 9 ? g(8) : 0.f;  // sumf, then + sums[0..7]
 #pragma unroll
@@ -535,7 +600,8 @@ __global__ __launch_bounds__(kBmT) void k_bmm(MVArgs A, const uint8_t* aq, const
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NW = EPI == EPI_SWIGLU ? 2 : 1;   // weight matrices (SWIGLU: gate, up)
     constexpr int NC = bm_nc<T, 0>();               // chains per (row, token)
-    constexpr int kBuf = kBmW * NW * 9 * 32;        // float4 per round buffer
+    constexpr int NS = bm_ns<T, 0>();               // term slots per (stage, matrix): 9 (Q2_K: 1)
+    constexpr int kBuf = kBmW * NW * NS * 32;       // float4 per round buffer
     float4* TmB = (float4*)smem;
     float4* G = TmB + 2 * kBuf;
     const int wave = uniform((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
@@ -585,7 +651,7 @@ __global__ __launch_bounds__(kBmT) void k_bmm(MVArgs A, const uint8_t* aq, const
                 for (int wi = 0; wi < NW; ++wi)
 #pragma unroll
                     for (int c = 0; c < NC; ++c)
-                        Tm[((wave * NW + wi) * 9 + c) * 32 + lane] =
+                        Tm[((wave * NW + wi) * NS + c) * 32 + lane] =
                             make_float4(tm[wi][c][0], tm[wi][c][1], tm[wi][c][2], tm[wi][c][3]);
             }
         }
@@ -599,14 +665,14 @@ __global__ __launch_bounds__(kBmT) void k_bmm(MVArgs A, const uint8_t* aq, const
                 const int wi = f / (NC * 32), c = (f / 32) % NC, L = f & 31;
                 float4 a = fs[k];
                 for (int w = 0; w < nv; ++w) {
-                    const float4 v = Tm[((w * NW + wi) * 9 + c) * 32 + L];
+                    const float4 v = Tm[((w * NW + wi) * NS + c) * 32 + L];
                     a.x += v.x;
                     a.y += v.y;
                     a.z += v.z;
                     a.w += v.w;
                 }
                 if (last) {  // the tile's chain results; the chains restart for the next tile
-                    G[(wi * 9 + c) * 32 + L] = a;
+                    G[(wi * NS + c) * 32 + L] = a;
                     a = make_float4(0.f, 0.f, 0.f, 0.f);
                 }
                 fs[k] = a;
@@ -654,10 +720,28 @@ typedef __attribute__((address_space(1))) void* bmd_glb_vp;
 // 2155 with one buffer, so one buffer is the default.  A row's 768 B are a multiple of the 256 B of
 // bank space, so beside the slot swizzle rows 8..15 swap each segment pair (seg ^ 1): the 16
 // rows of a read land on the 16 different 16-B columns, any 8 consecutive on 8 of one half.
+//
+// Q2_K: 5 segments per (matrix, row) -- the 4 A parts and the S plane, whose 16 B per unit are
+// always 16-B aligned and so ride the DMA with the quants; only the {d, dmin} dword of a stage is
+// a global load, a stage ahead (bm_load).  640 B per row and round.  LDS with the single term
+// slot (bm_ns): 4096 terms + 512 G + 10240 = 14848 B, SWIGLU 29696 B (static_assert below).
+// Banks (reasoned from the addresses, not measured): a piece sits at 640 p + 128 seg + 16 slot, p
+// the row's position in the buffer; 640 = 128 (mod 256), so its 16-B column of the 256 B of bank
+// space is 8 ((p ^ seg) & 1) + slot.  With p = row, the slot swizzle (stage ^ (row & 7)) gives
+// rows 0..7 eight different columns, but rows r and r + 8 share both slot and parity: a 2-way
+// conflict on every 16-row read.  A segment rotation cannot mend it: flipping the parity for
+// rows 8..15 needs a parity-flipping permutation of the 5 segment positions, and 5 is odd (3
+// even, 2 odd positions).  So the ROW position is permuted instead, p = row ^ (row >> 3)
+// (bmd_row_at: rows 8..15 swap in neighbouring pairs, an involution): rows r and r + 8 then
+// differ in parity, and the 16 rows of a read (one segment, one stage) meet the 16 different
+// columns.  The 4-B read of S dword g: bank 32 ((p ^ seg) & 1) + 4 slot + g, 64 different banks.
 template <int T>
-__host__ __device__ constexpr int bmd_nseg() { return T == T_Q3_K ? 6 : T == T_Q4_K ? 9 : T == T_Q5_K ? 11 : 13; }
+__host__ __device__ constexpr int bmd_nseg() { return T == T_Q2_K ? 5 : T == T_Q3_K ? 6 : T == T_Q4_K ? 9 : T == T_Q5_K ? 11 : 13; }
 template <int T>
-__host__ __device__ constexpr int bmd_nbuf() { return T == T_Q3_K ? LLMI_BMD_Q3K_BUFS : 1; }
+__host__ __device__ constexpr int bmd_nbuf() { return T == T_Q3_K ? LLMI_BMD_Q3K_BUFS : T == T_Q2_K ? LLMI_BMD_Q2K_BUFS : 1; }
+// the row whose pieces sit at position `pos` of a matrix's 16 rows in the round buffer, and back
+template <int T>
+__device__ __forceinline__ int bmd_row_at(int pos) { return T == T_Q2_K ? pos ^ (pos >> 3) : pos; }
 // bytes of a round's weight buffer
 template <int T, int NW>
 __host__ __device__ constexpr size_t bmd_wbytes() { return (size_t)NW * 16 * bmd_nseg<T>() * kBmW * 16; }
@@ -666,9 +750,10 @@ template <int T>
 __device__ __forceinline__ int bmd_seg_at(int seg, int row) { return T == T_Q3_K ? seg ^ ((row >> 3) & 1) : seg; }
 // plane base of segment `seg` of a row (unit u at + 16 u): A parts 0..7, then Q4_K the
 // header; Q5_K the header and the two fifth-bit parts; Q6_K the four high-bit parts and the
-// scales.  Q3_K: A parts 0..3, H parts 0, 1
+// scales.  Q3_K: A parts 0..3, H parts 0, 1.  Q2_K: A parts 0..3, the S plane
 template <int T>
 __device__ __forceinline__ const uint8_t* bmd_seg_base(const RowPtr& rp, int seg) {
+    if constexpr (T == T_Q2_K) return seg < 4 ? rp.qa + (uint32_t)seg * rp.ps : rp.sb;
     if constexpr (T == T_Q3_K) return seg < 4 ? rp.qa + (uint32_t)seg * rp.ps : rp.hb + (uint32_t)(seg - 4) * rp.ps;
     if (seg < 8) return rp.qa + (uint32_t)seg * rp.ps;
     if constexpr (T == T_Q4_K) return rp.sb;
@@ -683,7 +768,7 @@ __device__ __forceinline__ void bmd_dma(const MVArgs& A, int si, int row0, int r
     const int U = A.cols >> 8;
     for (int i = wave; i < NPC / 64; i += kBmW) {
         const int f = i * 64 + lane, q = f / kBmW, slot = f % kBmW;
-        const int seg = q % NSEG, rr = q / NSEG, row = rr % 16, mat = rr / 16;
+        const int seg = q % NSEG, rr = q / NSEG, row = bmd_row_at<T>(rr % 16), mat = rr / 16;
         const int u = min(rho * kBmW + (slot ^ (row & 7)), U - 1);
         const RowPtr rp = row_ptr<T>(pick(A, EPI == EPI_SWIGLU ? mat : si), row0 + row, A.cols);
         __builtin_amdgcn_global_load_lds((bmd_glb_vp)(bmd_seg_base<T>(rp, bmd_seg_at<T>(seg, row)) + (uint32_t)u * 16),
@@ -700,9 +785,15 @@ __device__ __forceinline__ void bmd_w(BmStage<T, NW>& st, const uint8_t* wb, int
 #pragma unroll
     for (int wi = 0; wi < NW; ++wi) {
         auto piece = [&](int seg) {
-            return wb + ((((size_t)(wi * 16 + row) * NSEG + bmd_seg_at<T>(seg, row)) * kBmW + slot) * 16);
+            return wb + ((((size_t)(wi * 16 + bmd_row_at<T>(row)) * NSEG + bmd_seg_at<T>(seg, row)) * kBmW + slot) * 16);
         };
         PfW<T>& w = st.w[wi];
+        if constexpr (T == T_Q2_K) {
+            // pf_w_load<T_Q2_K>'s view: chunk g = A part g, sc = S dword g; {d, dmin} came with bm_load
+            w.q0 = *(const u32x4*)piece(g);
+            w.sc = *(const uint32_t*)(piece(4) + 4 * g);
+            continue;
+        }
         if constexpr (T == T_Q3_K) {
             // pf_w_load<T_Q3_K>'s view: chunk g = A part g, its high bits in H part g / 2,
             // shifted down for the odd chunk; q1 (the scale bytes) and d came with bm_load
@@ -730,6 +821,9 @@ __host__ __device__ constexpr size_t bmd_lds() {
     return ((size_t)kBmW * NW * bm_ns<T, X86>() + (size_t)NW * bm_ns<T, X86>()) * 32 * 16 +
            (X86 ? (size_t)kBmW * NW * 16 * 8 + (size_t)kBmW * 8 * 4 : 0) + bmd_nbuf<T>() * bmd_wbytes<T, NW>();
 }
+static_assert(bmd_lds<T_Q2_K, 1, 0>() == 14848 + (LLMI_BMD_Q2K_BUFS - 1) * 10240 &&
+                  bmd_lds<T_Q2_K, 2, 0>() == 29696 + (LLMI_BMD_Q2K_BUFS - 1) * 20480,
+              "Q2_K k_bmd: one term slot and five segments (about 15 KB per workgroup, SWIGLU 29 KB)");
 
 // the persistent tile loop of one k_bmd workgroup: tiles tile0, tile0 + stride, ... < ntiles.
 // X86: the fold runs the x86 fma chains, a = fma(d, term, a) with d = d_w d_a (lanes) or
@@ -883,7 +977,7 @@ __global__ __launch_bounds__(kBmT) void k_bmd2(MVArgs A1, MVArgs A2, const uint8
 }
 
 // ---- launchers -----------------------------------------------------------------------------
-#if !LLMI_BATCH_Q3K
+#if !LLMI_BATCH_SUB
 size_t mvn_lds_bytes(int act, int cols, int nt, int x86) {
     const size_t fold = x86 ? (act ? (size_t)kX86QFloats : (size_t)kX86KFloats) : (size_t)kFoldFloats;
     (void)fold;
@@ -957,6 +1051,10 @@ static hipError_t mvn_epi(const MVArgs& a, int epi, int nt, int mb, hipStream_t 
 hipError_t mvn_q3k(const MVArgs& a, int epi, int nt, int max_blocks, hipStream_t s) {
     return mvn_epi<0, T_Q3_K, 0>(a, epi, nt, max_blocks, s);
 }
+#elif LLMI_BATCH_Q2K
+hipError_t mvn_q2k(const MVArgs& a, int epi, int nt, int max_blocks, hipStream_t s) {
+    return mvn_epi<0, T_Q2_K, 0>(a, epi, nt, max_blocks, s);
+}
 #else
 static hipError_t mvn_type(const MVArgs& a, int epi, int nt, int max_blocks, hipStream_t s) {
     if (a.num) {  // x86 association
@@ -974,6 +1072,7 @@ static hipError_t mvn_type(const MVArgs& a, int epi, int nt, int max_blocks, hip
         case T_Q6_K: return mvn_epi<0, T_Q6_K, 0>(a, epi, nt, max_blocks, s);
         case T_Q8_0: return mvn_epi<1, T_Q8_0, 0>(a, epi, nt, max_blocks, s);
         case T_Q3_K: return mvn_q3k(a, epi, nt, max_blocks, s);  // generic numerics only
+        case T_Q2_K: return mvn_q2k(a, epi, nt, max_blocks, s);  // generic numerics only
         default: return hipErrorInvalidValue;
     }
 }
@@ -1030,14 +1129,14 @@ static int bmm_dma() {
     return e ? atoi(e) : 1;
 }
 
-#if !LLMI_BATCH_Q3K
+#if !LLMI_BATCH_SUB
 bool bmm_ok(const MVArgs& a, int epi) {
     if (!g_bmm_env || a.nseg < 1 || a.cols <= 0 || a.cols % 256) return false;
     if (a.num && !bmm_dma()) return false;  // the x86 fold is k_bmd's only
     for (int i = 0; i < a.nseg; ++i)
         if ((a.seg[i].x86 != 0) != (a.num != 0)) return false;  // the planes' byte order
     const int t = a.seg[0].type;
-    if (!(t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || (t == T_Q3_K && !a.num))) return false;  // Q3_K: generic numerics only
+    if (!(t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || ((t == T_Q3_K || t == T_Q2_K) && !a.num))) return false;  // Q3_K, Q2_K: generic numerics only
     if (epi == EPI_SWIGLU && (a.nseg != 2 || a.seg[0].rows != a.seg[1].rows)) return false;
     for (int i = 0; i < a.nseg; ++i) {
         if (a.seg[i].type != t || a.seg[i].rows % 16) return false;
@@ -1073,7 +1172,7 @@ static hipError_t bmm_launch(const MVArgs& a, const void* aq, const void* abf, c
     constexpr int NW = EPI == EPI_SWIGLU ? 2 : 1;
     const bool dma = X86 || bmm_dma() != 0;
     auto k = dma ? k_bmd<T, EPI, X86> : k_bmm<T, EPI>;
-    const size_t lds = dma ? bmd_lds<T, NW, X86>() : (size_t)(2 * kBmW + 1) * NW * 9 * 32 * 16;
+    const size_t lds = dma ? bmd_lds<T, NW, X86>() : (size_t)(2 * kBmW + 1) * NW * bm_ns<T, 0>() * 32 * 16;
     // shape / occupancy rejections are hipErrorNotSupported: the caller then runs the two
     // type groups as separate launches (decode_step.cpp) instead of failing the step
     if (lds > 160 * 1024) return hipErrorNotSupported;
@@ -1123,6 +1222,13 @@ hipError_t bmm2_q3k(const MVArgs& a1, const MVArgs& a2, const void* aq, const vo
     if (a2.seg[0].type == T_Q5_K) return bmm2_launch<T_Q3_K, T_Q5_K, 0>(a1, a2, aq, abf, ad, nt, s);
     return hipErrorNotSupported;
 }
+#elif LLMI_BATCH_Q2K
+// the QKV of Q2_K files: q / k in Q2_K, attn_v in Q3_K or Q4_K (kernels.hip LLMI_QKV2's pairs)
+hipError_t bmm2_q2k(const MVArgs& a1, const MVArgs& a2, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s) {
+    if (a2.seg[0].type == T_Q3_K) return bmm2_launch<T_Q2_K, T_Q3_K, 0>(a1, a2, aq, abf, ad, nt, s);
+    if (a2.seg[0].type == T_Q4_K) return bmm2_launch<T_Q2_K, T_Q4_K, 0>(a1, a2, aq, abf, ad, nt, s);
+    return hipErrorNotSupported;
+}
 #else
 // LLMI_BMM2 (A/B): 1 mixed-type QKV in one k_bmd2 launch (default), 0 two launches
 static int bmm2_on() {
@@ -1146,6 +1252,7 @@ hipError_t launch_bmm_qkv2(const MVArgs& a1, const MVArgs& a2, int nt, const voi
     if (t1 == T_Q4_K && t2 == T_Q5_K) return bmm2_launch<T_Q4_K, T_Q5_K, 0>(a1, a2, aq, abf, ad, nt, s);
     if (t1 == T_Q5_K && t2 == T_Q6_K) return bmm2_launch<T_Q5_K, T_Q6_K, 0>(a1, a2, aq, abf, ad, nt, s);
     if (t1 == T_Q3_K) return bmm2_q3k(a1, a2, aq, abf, ad, nt, s);
+    if (t1 == T_Q2_K) return bmm2_q2k(a1, a2, aq, abf, ad, nt, s);
     return hipErrorNotSupported;
 }
 #endif
@@ -1166,6 +1273,10 @@ static hipError_t bmm_epi(const MVArgs& a, int epi, const void* aq, const void* 
 hipError_t bmm_q3k(const MVArgs& a, int epi, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s) {
     return bmm_epi<T_Q3_K, 0>(a, epi, aq, abf, ad, nt, s);
 }
+#elif LLMI_BATCH_Q2K
+hipError_t bmm_q2k(const MVArgs& a, int epi, const void* aq, const void* abf, const float* ad, int nt, hipStream_t s) {
+    return bmm_epi<T_Q2_K, 0>(a, epi, aq, abf, ad, nt, s);
+}
 #else
 hipError_t launch_bmm(const MVArgs& a, int epi, int nt, const void* aq, const void* abf, const float* ad, hipStream_t s) {
     if (nt < 1 || nt > kMaxBatch || !bmm_ok(a, epi)) return hipErrorInvalidValue;
@@ -1182,6 +1293,7 @@ hipError_t launch_bmm(const MVArgs& a, int epi, int nt, const void* aq, const vo
         case T_Q5_K: return bmm_epi<T_Q5_K, 0>(a, epi, aq, abf, ad, nt, s);
         case T_Q6_K: return bmm_epi<T_Q6_K, 0>(a, epi, aq, abf, ad, nt, s);
         case T_Q3_K: return bmm_q3k(a, epi, aq, abf, ad, nt, s);
+        case T_Q2_K: return bmm_q2k(a, epi, aq, abf, ad, nt, s);
         default: return hipErrorInvalidValue;
     }
 }

@@ -397,7 +397,7 @@ int32_t llmi_bmv(int32_t type, const void* w, int64_t rows, int64_t cols, const 
     a.nw = nw; a.eps = eps;
     a.x_stride = (int)cols; a.y_stride = (int)rows;
     a.num = t_hook_numerics & NUMERICS_X86;
-    if (type == T_Q2_K) {  // neither k_mvn nor the matrix-core kernels are instantiated for it
+    if (type == T_Q2_K) {  // this hook declines the type; its kernels exist (batch_q2k.hip), reached through llmi_mv_epilogue
         set_err("llmi_bmv: no batched kernels for q2_K weights");
         return -1;
     }

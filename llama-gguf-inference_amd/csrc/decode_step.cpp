@@ -349,21 +349,16 @@ static bool bstep_enqueue(Context& c, int nt, const int* seqs, int kv_bound, std
 
 // the batched step in this model's numerics: every numerics and weight type (generic and
 // x86 K-quant rows on the matrix cores from 3 tokens, the rest through k_mvn; x86 Q8_0
-// rows with 4 working waves per workgroup, batch.hip mvn_work_waves; Q3_K rows, generic
-// numerics only, through the same kernels: batch_q3k.hip).  A layer whose
-// ffn_gate and ffn_up differ in type has no batched step in any numerics, nor has a model
-// with a Q2_K tensor (bstep_run's errors; llama_decode then steps such sequences one at a time)
+// rows with 4 working waves per workgroup, batch.hip mvn_work_waves; Q3_K and Q2_K rows,
+// generic numerics only, through the same kernels: batch_q3k.hip, batch_q2k.hip; a QKV
+// whose type pair k_bmd2 is not instantiated for runs as one launch per type group).  A layer
+// whose ffn_gate and ffn_up differ in type has no batched step in any numerics (bstep_run's
+// error; llama_decode then steps such sequences one at a time)
 bool bstep_run(Context& c, int nt, const int* seqs, int max_pos, std::string& err, int tail) {
     const HParams& hp = c.m->hp;
     if (nt < 1 || nt > kMaxBatch || c.n_seq < 2) { err = "batched step: 1..8 slots of a context with n_seq_max >= 2"; return false; }
     for (const Layer& L : c.m->layers)
         if (L.wg.type != L.wu.type) { err = "batched step: ffn_gate / ffn_up of different types"; return false; }
-    // Q2_K has no batched kernels (k_mvn / k_bmd / k_bmm): such a model steps its sequences one at a time
-    auto q2 = [](const DevMat& d) { return d.type == T_Q2_K; };
-    bool has_q2 = q2(c.m->tok_embd) || q2(c.m->output);
-    for (const Layer& L : c.m->layers)
-        has_q2 = has_q2 || q2(L.wq) || q2(L.wk) || q2(L.wv) || q2(L.wo) || q2(L.wg) || q2(L.wu) || q2(L.wd);
-    if (has_q2) { err = "batched step: no batched kernels for q2_K weights"; return false; }
     if (!balloc(c, err)) return false;
     const int bucket = max_pos / 256;
     const int kv_bound = kv_bucket_bound(max_pos + 1, c.n_ctx);
